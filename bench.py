@@ -1,16 +1,24 @@
 """Benchmark of the hot path: ConQueR / Voxel-DETR single-frame Waymo TRAINING STEP on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                  (also write what the last timed step computed, as .npy)
+    python bench.py ... --full                              (also every side measurement and check below)
 
 A step = voxelize (GPU) -> sparse-conv backbone -> BEV/FPN -> box-attention DETR enc/dec -> 32 losses (device
 Hungarian matching) -> backward -> (gradient all-reduce over RCCL) -> AdamW + OneCycle schedule, on `--scenes`
 synthetic Waymo-shaped scenes per GPU that are resident in HBM before the timed region.  Prints ONE JSON line (rank 0).
 
-The timed region is clean: no event records, no count read-backs for accounting.  The per-kernel numbers (`roofline`,
-`kernels`, `geometry`) come from `--profile-steps` EXTRA steps after the timed region, with HIP events on the launch
-stream around every launch of our kernels; `full_graph` is a second, shorter timing of the same step with the FPN
-levels / heads the reference evaluates and never reads; `cpu_baseline` is the reference / oracle on the
-host cores (N = 1 only).
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs` and prints the line: nothing else.  The
+ConQueR / Voxel-DETR process runs with EFG_DETERMINISTIC=1 unless the environment sets it: two runs with the same
+arguments compute the same bits.
+The timed region is clean: no event records, no count read-backs for accounting.
+
+Only with `--full`: the per-kernel numbers (`roofline`, `kernels`, `geometry`) from `--profile-steps` EXTRA steps after
+the timed region, with HIP events on the launch stream around every launch of our kernels; the per-rank facts
+(`rank_input_voxels`, `streamk_fallbacks`, `host_own_ms_per_step`); the bf16x3 A/B arm; the `steady_state` soak;
+`full_graph`, a second, shorter timing of the same step with the FPN levels / heads the reference evaluates and never
+reads; `yaml_config` (1000 queries); `cpu_baseline` and `parity_full_size`, the reference / oracle on
+the host cores (N = 1 only).
 """
 import argparse
 import json
@@ -48,7 +56,15 @@ def parse():
                     help="BASELINE.json configs[2]: 900 queries (the reference YAML's own default is 1000: the line's "
                          "`yaml_config` object times that)")
     ap.add_argument("--pool", type=int, default=2, help="distinct synthetic batches cycled through")
-    ap.add_argument("--profile-steps", type=int, default=3, help="extra, untimed steps with per-kernel HIP events")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline timing, every side measurement and check as well (per-kernel profile, per-rank "
+                         "facts, A/B arm, soak, full graph, 1000 queries, CPU baseline + full-size parity); off: the plain "
+                         "run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (every loss term, the total loss, a fixed sample of the "
+                         "updated parameters and of their gradients) as DIR/<name>.npy; the inputs depend only on the "
+                         "arguments, so two builds can be compared output for output")
+    ap.add_argument("--profile-steps", type=int, default=3, help="--full: extra, untimed steps with per-kernel HIP events")
     ap.add_argument("--soak-steps", type=int, default=300,
                     help="N > 0: after the timed run, N more optimizer steps on a 4-batch pool, then the step timed again -> the "
                          "line's `steady_state` object (the encoder's boxes grow as training proceeds; the default is a ~10 s "
@@ -62,7 +78,10 @@ def parse():
                          "three flat buckets all-reduced on a communication stream while backward still runs (what the "
                          "reference's DDP does; not the default, see engine.py); static / find_unused / plain = torch "
                          "DistributedDataParallel variants")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _pmc_traffic(kernel):
@@ -298,6 +317,37 @@ def _rank_report(trainer, batch, world, dev):
     return {"rank_input_voxels": [int(t[0]) for t in every], "streamk_fallbacks": [int(t[1]) for t in every]}
 
 
+_DUMP_SAMPLE = 1 << 22   # elements of a sampled array in --dump-outputs: 16 MB of float32
+
+
+def _dump_outputs(out_dir, model, result):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy in float32.  What `Trainer.step` hands its
+    caller -- every loss term (`<term>.npy`) and their sum (`total_loss.npy`) -- and what the step left in the model: the
+    updated parameters (`params.npy`) and their gradients (`grads.npy`, zero for a parameter without one), flattened in
+    `model.parameters()` order.  Past _DUMP_SAMPLE elements those two are a fixed sample: the same seeded, sorted positions
+    in every run of the same model (2 x 16 MB at most)."""
+    import re
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    loss_dict, total = result
+    arrays = {k: v for k, v in loss_dict.items() if torch.is_tensor(v)}
+    arrays["total_loss"] = total
+    params = list(model.parameters())
+    flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+    flat_g = torch.cat([p.grad.detach().reshape(-1).float() if p.grad is not None else
+                        torch.zeros(p.numel(), dtype=torch.float32, device=p.device) for p in params])
+    if flat_p.numel() > _DUMP_SAMPLE:
+        pick = torch.randperm(flat_p.numel(), generator=torch.Generator().manual_seed(0))[:_DUMP_SAMPLE].sort().values
+        pick = pick.to(flat_p.device)
+        flat_p, flat_g = flat_p[pick], flat_g[pick]
+    arrays["params"], arrays["grads"] = flat_p, flat_g
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, re.sub(r"[^A-Za-z0-9_.-]", "_", name) + ".npy"),
+                t.detach().float().cpu().numpy())
+
+
 def _pin_rank(local_rank, world):
     """N > 1: every rank's threads (Python main + autograd thread, ROCr's event thread: ~2 busy cores per rank, DESIGN.md
     section 8) on a slice of the CPUs this process may use that no other rank of the node gets -- eight ranks otherwise
@@ -373,6 +423,8 @@ def main():
                          "or run `python bench.py --gpus %d` bare and it starts the ranks itself)"
                          % (args.gpus, world, args.gpus, args.gpus))
     dev = torch.device("cuda", local_rank % torch.cuda.device_count())
+    if args.dump_outputs and args.model not in ("conquer", "voxeldetr"):
+        raise SystemExit("bench.py: --dump-outputs covers the ConQueR / Voxel-DETR step (--model conquer | voxeldetr)")
     if args.model == "trajectoryformer":
         from efg_amd.tracking.bench import run as run_tracking
 
@@ -381,6 +433,13 @@ def main():
         from efg_amd.centerpoint.bench import run as run_centerpoint
 
         return run_centerpoint(args, rank, local_rank, world, dev)
+    # Every step of this process is run-to-run reproducible: two runs with the same arguments compute the same bits (what
+    # --dump-outputs compares).  Everything of ours on the path has a fixed summation order; the one layer that does not is
+    # the dense 3 x 3 FPN convolution on MIOpen (float atomics in its weight gradient), which EFG_DETERMINISTIC=1 runs as
+    # fixed-order GEMMs instead (operators/conv2d.py; +0.85 ms per step).  Set for the whole process,
+    # so that the --full side timings (arm, soak, full graph, 1000 queries) differ from `value` only in what they name.
+    # An explicit EFG_DETERMINISTIC in the environment wins.
+    os.environ.setdefault("EFG_DETERMINISTIC", "1")
     config = None if args.model == "conquer" else os.path.join(ROOT, "configs", "voxeldetr_waymo_res18.yaml")
     overrides = {"model.transformer.num_queries": args.queries}
     if args.full_graph:
@@ -406,9 +465,11 @@ def main():
             tr.step(pool[w % len(pool)])
         barrier()
         t0 = time.perf_counter()
-        for s in range(steps):
+        for s in range(steps - 1):
             tr.step(pool[s % len(pool)])
+        last = tr.step(pool[(steps - 1) % len(pool)])   # (loss dict, total) of the last timed step: --dump-outputs
         issued = time.perf_counter() - t0     # the host has QUEUED the last step here; the device may still be running
+        stats["last"] = last
         barrier()
         elapsed = time.perf_counter() - t0
         stats["host_issue_ms_per_step"] = 1000.0 * issued / steps
@@ -464,23 +525,28 @@ def main():
                              "all": [round(t, 3) for t in stats["rank_ms_per_step"]]},
         "host_issue_ms_per_step": round(stats["host_issue_ms_per_step"], 3),
     }
-    line.update(_rank_report(trainer, pool[0], world, dev))
-    own = torch.tensor([_host_own_ms(trainer, pool, dev)], device=dev, dtype=torch.float64)
-    every = [own]
-    if world > 1:
-        every = [torch.zeros_like(own) for _ in range(world)]
-        dist.all_gather(every, own)
-    line["host_own_ms_per_step"] = [round(float(t[0]), 3) for t in every]   # per rank, from empty queues (see _host_own_ms)
     line["rank_cpu_slice"] = pinned                                           # rank 0's [first, last] CPU, None = not pinned
     line["hw_queues"] = os.environ.get("GPU_MAX_HW_QUEUES")
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, trainer.model, stats["last"])
+    line["deterministic"] = os.environ["EFG_DETERMINISTIC"] == "1"
+    # ---- everything below runs with --full only: a plain run prints the line now ------------------------------------
+    if args.full:
+        line.update(_rank_report(trainer, pool[0], world, dev))
+        own = torch.tensor([_host_own_ms(trainer, pool, dev)], device=dev, dtype=torch.float64)
+        every = [own]
+        if world > 1:
+            every = [torch.zeros_like(own) for _ in range(world)]
+            dist.all_gather(every, own)
+        line["host_own_ms_per_step"] = [round(float(t[0]), 3) for t in every]   # per rank, from empty queues (_host_own_ms)
     # ---- per-kernel numbers: extra steps, outside the timed region ------------------------------------------------
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         _prof.enable(True)
         for s in range(args.profile_steps):
             trainer.step(pool[s % len(pool)])
         barrier()
         _prof.enable(False)
-    if rank == 0:
+    if rank == 0 and args.full:
         summ = _prof.summary() if args.profile_steps > 0 else {}
         roof = _prof.roofline() if summ else None
         if roof is not None:
@@ -530,7 +596,7 @@ def main():
     # the difference is the products and nothing else (a second model in the process draws new physical memory and, before
     # efg_amd/streams.py, new hardware queues: one model in three came out 2-3 ms slower).
     arm_on = os.environ.get("EFG_GEMM_ARM", "") == "bf16x3"
-    if not args.no_arm and not arm_on and world == 1 and args.model in ("conquer", "voxeldetr"):
+    if args.full and not args.no_arm and not arm_on and world == 1 and args.model in ("conquer", "voxeldetr"):
         import efg_amd.operators.linear as _lin
 
         _lin._ARM_BF16X3 = True
@@ -544,7 +610,9 @@ def main():
                          "convolution (EFG_CONV2D_ARM; three products per pass over overlapping-row views of the padded map) as "
                          "hi.hi + hi.lo + lo.hi of bf16-split operands, fp32 accumulate (csrc/gemm_bf16x3.hip, csrc/spconv_tiles.hip); "
                          "everything else exact fp32",
-                "note": "A/B arm, not the headline: `value` above is the exact-fp32 step"}
+                "note": "A/B arm, not the headline: `value` above is the exact-fp32 step" + (
+                        "; EFG_DETERMINISTIC=1: the neck convolution runs as the same fixed-order fp32 GEMMs in both timings "
+                        "(EFG_CONV2D_ARM does not apply)" if os.environ.get("EFG_DETERMINISTIC") == "1" else "")}
         finally:
             _lin._ARM_BF16X3 = False
     trainer.close()
@@ -553,7 +621,7 @@ def main():
     # corners take the binned path).  The timed trainer above is at the start of the config's long schedule, where nothing
     # moves yet: this one gets a one-cycle schedule of exactly N + steps iterations (as scripts/ubench/soak.py does), so the
     # weights move as far in N steps as they do over a training run.
-    if args.soak_steps > 0 and world == 1:
+    if args.full and args.soak_steps > 0 and world == 1:
         del trainer
         torch.cuda.empty_cache()
         soak_tr = Trainer(config=config, device=dev, overrides=overrides, seed=0, max_iters=args.soak_steps + 2 * args.steps + args.warmup + 10)
@@ -578,7 +646,7 @@ def main():
                                         "synthetic batches: timed fresh, run --soak-steps optimizer steps, timed again"}
         trainer = None
     # ---- the same step with the reference's dead branches evaluated ----------------------------------
-    if not args.no_full_graph and not args.full_graph and world == 1:
+    if args.full and not args.no_full_graph and not args.full_graph and world == 1:
         del trainer
         torch.cuda.empty_cache()
         ov = dict(overrides)
@@ -591,7 +659,7 @@ def main():
                               "note": "also evaluates FPN p2 / p4-output / p5 and res2_out like the reference; "
                                       "same losses and gradients"}
     # ---- `value` is BASELINE.json configs[2] (900 queries); the reference YAML's own default is 1000 ------------------------
-    if args.queries != 1000 and world == 1 and not args.no_full_graph and args.model == "conquer":
+    if args.full and args.queries != 1000 and world == 1 and not args.no_full_graph and args.model == "conquer":
         torch.cuda.empty_cache()
         ov = dict(overrides)
         ov["model.transformer.num_queries"] = 1000
@@ -605,7 +673,7 @@ def main():
                                "note": "the same step with the reference YAML's 1000 queries; `value` is BASELINE.json "
                                        "configs[2]'s 900 (per-GPU share of the batch-16 / 8-GPU config: 2 scenes)"}
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             base = cpu_baseline(args)
             line["parity_full_size"] = base.pop("parity_full_size")
             line["cpu_baseline"] = base

@@ -57,14 +57,14 @@ def run(args, rank, local_rank, world, dev):
                                % (args.sweeps, args.points, 5 if args.sweeps == 1 else 6, args.scenes),
                    "global_batch": args.scenes * world, "parallelism": "dp%d" % world},
     }
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:   # per-kernel numbers: bench.py --full only
         _prof.enable(True)
         for s in range(args.profile_steps):
             trainer.step(pool[s % len(pool)])
         barrier()
         _prof.enable(False)
     if rank == 0:
-        summ = _prof.summary() if args.profile_steps > 0 else {}
+        summ = _prof.summary() if args.full and args.profile_steps > 0 else {}
         roof = _prof.roofline() if summ else None
         if roof is not None:
             roof["measured"] = "HIP events on the launch stream, %d extra steps after the timed region" % args.profile_steps

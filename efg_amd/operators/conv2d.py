@@ -13,7 +13,7 @@ CONTIGUOUS row range, so with off(ky, kx) = (ky - 1) (W + 2) + (kx - 1) over the
     dW[:, :, ky, kx] =     sum_r  G_pad[r]^T  X_pad[r + off_k]     nine `operators.linear.weight_grad` (16 fixed row chunks)
 
 (the border rows of Y and dX are computed and dropped; the padding rows of G are zero, so every out-of-image pair drops out
-of dW).  hipBLASLt does not split K = 256, so each product has one summation order.  +0.5 ms per step, hence opt-in."""
+of dW).  hipBLASLt does not split K = 256, so each product has one summation order.  +0.85 ms per step: opt-in for training; bench.py runs it."""
 import os
 
 import torch

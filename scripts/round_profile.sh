@@ -8,10 +8,10 @@ host_state() { echo "loadavg $(cat /proc/loadavg) | $(grep -E 'nr_throttled|thro
 host_state > $out/host_state.txt
 python bench.py --no-cpu-baseline --no-full-graph --no-arm --steps 10 > /dev/null 2>&1   # page the image in; the first process on a fresh box is slow
 host_state >> $out/host_state.txt
-python bench.py > $out/bench.json 2> $out/bench.stderr
+python bench.py --full > $out/bench.json 2> $out/bench.stderr
 host_state >> $out/host_state.txt
 tail -c 600 $out/bench.json
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/$tag.ks -o r -- python bench.py --no-cpu-baseline --no-full-graph --no-arm > $out/bench_under_rocprof.json 2> $out/rocprof.stderr
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/$tag.ks -o r -- python bench.py --full --no-cpu-baseline --no-full-graph --no-arm > $out/bench_under_rocprof.json 2> $out/rocprof.stderr
 cp /tmp/$tag.ks/r_kernel_stats.csv $out/kernel_stats.csv
 for ctr in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/$tag.$ctr && mkdir -p /tmp/$tag.$ctr

@@ -35,7 +35,7 @@ def _torchrun(script_args, mode, backend="gloo"):
 
 
 _BENCH_ARGS = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--points", "30000", "--queries", "100", "--scenes", "1",
-               "--no-cpu-baseline", "--profile-steps", "1"]
+               "--no-cpu-baseline", "--profile-steps", "1", "--full"]
 
 
 def _check_line(r, mode="flat", backend="gloo"):
@@ -63,6 +63,24 @@ def test_bench_two_ranks_one_gpu(dev, mode):
     (engine.default_ddp_mode; test_rccl_two_ranks_when_the_node_has_two_devices)"""
     args = ["bench.py"] + _BENCH_ARGS + (["--ddp-mode", mode] if mode else [])
     _check_line(_torchrun(args, None), mode or "flat")
+
+
+def test_bench_two_ranks_plain_run(dev, tmp_path):
+    """the plain N > 1 run (no --full): every rank times its steps, rank 0 prints the headline and dumps the outputs of
+    its last timed step, no rank waits on a collective the others skip"""
+    out = tmp_path / "outputs"
+    args = ["bench.py"] + [a for a in _BENCH_ARGS if a != "--full"] + ["--dump-outputs", str(out)]
+    r = _torchrun(args, None)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:] + r.stderr[-3000:]
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 2 and line["steps"] == 2 and line["value"] > 0 and line["rccl_ranks"] == 2
+    assert len(line["rank_ms_per_step"]["all"]) == 2 and line["rank_ms_per_step"]["max"] == pytest.approx(line["ms_per_step"], rel=1e-3)
+    assert 0 < line["host_issue_ms_per_step"] <= line["ms_per_step"] * 1.001
+    for key in ("rank_input_voxels", "streamk_fallbacks", "host_own_ms_per_step", "roofline", "kernels"):
+        assert key not in line, key
+    assert (out / "total_loss.npy").exists() and (out / "params.npy").exists()
 
 
 def test_bench_bare_command_starts_its_own_ranks(dev):
@@ -119,7 +137,8 @@ def test_bench_two_ranks_other_models(dev, model):
     head are channels-last on the GPU: the exchange has to hand every parameter its gradient in the parameter's own layout
     (engine._flat_view), or the fused optimizer refuses the step."""
     r = _torchrun(["bench.py", "--model", model, "--gpus", "2", "--steps", "2", "--warmup", "1", "--points", "30000",
-                   "--scenes", "1", "--objects", "20", "--no-cpu-baseline", "--profile-steps", "1", "--soak-steps", "0"], None)
+                   "--scenes", "1", "--objects", "20", "--no-cpu-baseline", "--profile-steps", "1", "--soak-steps", "0",
+                   "--full"], None)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads(lines[0])
