@@ -21,7 +21,7 @@ import torch.nn.functional as F
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from .linear import weight_grad
+from .linear import arm_module, weight_grad
 
 
 def deterministic_mode():
@@ -113,14 +113,23 @@ def _tap_rows(buf, start_row, rows, c):
     return buf.as_strided((rows, 3 * c), (c, 1), buf.storage_offset() + start_row * c)
 
 
+def _arm_products():
+    """operators/gemm_bf16x6.py when the x6 arm alone is switched on, else operators/gemm_bf16x3.py (also with no switch set:
+    conv3x3_arm called by hand is the x3 arm, as it was before there were two)."""
+    G = arm_module()
+    if G is None:
+        from . import gemm_bf16x3 as G
+    return G
+
+
 class Conv3x3ArmFunction(Function):
-    """The same convolution on the split-precision A/B arm (EFG_GEMM_ARM=bf16x3; never the default): per ky ONE product of
-    the overlapping-row view above with the [3 Ci, Co] block of the weights (csrc/gemm_bf16x3.hip takes the row stride as an
+    """The same convolution on the split-precision arms (EFG_GEMM_ARM=bf16x3 or bf16x6; never the default): per ky ONE product of
+    the overlapping-row view above with the [3 Ci, Co] block of the weights (csrc/gemm_bf16x3.hip / gemm_bf16x6.hip take the row stride as an
     argument), three products per pass instead of MIOpen's implicit GEMM -- forward, data gradient and weight gradient."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        from . import gemm_bf16x3 as G
+        G = _arm_products()
 
         b, ci, h, w = x.shape
         co = weight.shape[0]
@@ -140,7 +149,7 @@ class Conv3x3ArmFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, gy):
-        from . import gemm_bf16x3 as G
+        G = _arm_products()
 
         xb, weight = ctx.saved_tensors
         b, h, w = ctx.geom

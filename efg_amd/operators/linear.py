@@ -65,12 +65,50 @@ _ARM_BF16X3 = os.environ.get("EFG_GEMM_ARM", "") == "bf16x3"
 # forward packs both layouts in one launch and hands the data-gradient one to the backward.)
 
 
+# The fp32-equivalent arm (EFG_GEMM_ARM=bf16x6, never the default either): the same products of the same shapes as six
+# bf16 MFMA products of operands split into three pieces (csrc/gemm_bf16x6.hip) -- the error of an fp32 product.  With both
+# switches on, x3 wins: the bench's own arm leg sets _ARM_BF16X3 and keeps measuring what it measures.
+_ARM_BF16X6 = os.environ.get("EFG_GEMM_ARM", "") == "bf16x6"
+
+
+def arm_module():
+    """The module of split products the switches select (read at call time: tests and the bench flip them), None with both off."""
+    if _ARM_BF16X3:
+        from . import gemm_bf16x3 as G
+
+        return G
+    if _ARM_BF16X6:
+        from . import gemm_bf16x6 as G
+
+        return G
+    return None
+
+
 def _arm_ok(a2, min_cols=64):
     """a2: the [rows, K] operand of a product: the long matrices only (the decoder-sized Linear + ReLU layers also come
     through LinearFunction since round 4 and stay exact fp32).  Below K = 64 the split product loses to fp32 (op bench: 32 -> 256 29.6 vs
     26.2 us; the 32-row weight gradient 44.5 vs 28.5 us)."""
-    return (_ARM_BF16X3 and a2.dim() == 2 and a2.stride(1) == 1 and a2.shape[1] % 4 == 0 and a2.stride(0) % 4 == 0
-            and a2.data_ptr() % 16 == 0 and a2.shape[0] >= _FUSED_MIN_ROWS and a2.shape[1] >= min_cols)
+    return ((_ARM_BF16X3 or _ARM_BF16X6) and a2.dim() == 2 and a2.stride(1) == 1 and a2.shape[1] % 4 == 0
+            and a2.stride(0) % 4 == 0 and a2.data_ptr() % 16 == 0 and a2.shape[0] >= _FUSED_MIN_ROWS
+            and a2.shape[1] >= min_cols)
+
+
+# x6's own floor for the forward / data-gradient product [rows, K] x [K, N] (profiles/gemm_bf16x6_ops.txt, x6 / library
+# fp32 time at 70 688 rows): K = 256 -> N = 256 / 1024 / 232: 0.85-0.94 / 0.80 / 0.80, K = 384 -> 256: 0.75-0.86,
+# K = 1024 -> 256: 0.81-0.84, but K = 200 / 232 -> 256 (the data gradient of the attention logits): 1.11 / 1.10 -- the
+# library's product shrinks with K, the split one is bound by its A and C traffic.  So x6 takes K >= 256; x3 keeps K >= 64.
+# Left as they are, and measured slower than the library: the weight gradients of the 256- and 232-wide layers (1.05-1.08,
+# 4-6 us each; they are 2-10 x more accurate than the library's 16-chunk product, and the 1024-wide ones win, 0.94) and the one
+# 17 672-row layer of the step (coarse BEV 1 x 1, 512 -> 256: 1.15 forward, 1.11 data gradient, +12 us per step; 277
+# workgroups do not fill 256 CUs x 3) -- the row floor stays the arm's 16 384.
+_X6_MIN_K = 256
+
+
+def _arm_gemm(a2):
+    """The module whose `gemm` takes the product of a2 [rows, K] with a [K, N] weight, or None for the library."""
+    if not _arm_ok(a2) or (not _ARM_BF16X3 and a2.shape[1] < _X6_MIN_K):
+        return None
+    return arm_module()
 
 
 def weight_grad(x2, g2):
@@ -80,9 +118,7 @@ def weight_grad(x2, g2):
     matrices take 85 us (scripts/ubench/wgrad_split.py: 333 -> 262 us for the 1024-wide FFN layers, 138 -> 76 us
     for the 200-wide attention logits).  Deterministic, same fp32 products."""
     if _arm_ok(x2) and _arm_ok(g2):
-        from . import gemm_bf16x3 as G
-
-        return G.wgrad(g2, x2)
+        return arm_module().wgrad(g2, x2)
     k = x2.shape[0]
     if k >= _SPLIT_MIN_ROWS and k % _SPLITS == 0 and x2.is_contiguous() and g2.is_contiguous():
         gs = g2.view(_SPLITS, k // _SPLITS, g2.shape[1])
@@ -101,9 +137,8 @@ class LinearFunction(Function):
     def forward(ctx, x, weight, bias, relu=False):
         x2 = x.reshape(-1, x.shape[-1])
         ctx.packed_dgrad = None
-        if _arm_ok(x2):
-            from . import gemm_bf16x3 as G
-
+        G = _arm_gemm(x2)
+        if G is not None:
             packed_fwd, ctx.packed_dgrad = G.pack_linear_both(weight.detach())
             y = G.gemm(x2, packed_fwd, weight.shape[0], bias=bias, relu=relu)
         elif relu and bias is not None and x2.shape[0] >= _FUSED_MIN_ROWS:
@@ -135,9 +170,8 @@ class LinearFunction(Function):
                 g2, gb = relu_backward_column_sum(g2, y)   # threshold_backward + bias gradient in one pass
             else:
                 g2 = torch.ops.aten.threshold_backward(g2, y, 0)  # what autograd runs for relu
-        if ctx.needs_input_grad[0] and _arm_ok(g2):
-            from . import gemm_bf16x3 as G
-
+        G = _arm_gemm(g2) if ctx.needs_input_grad[0] else None
+        if G is not None:
             packed = ctx.packed_dgrad if ctx.packed_dgrad is not None else G.pack_linear(weight.detach(), True)
             gx = G.gemm(g2, packed, weight.shape[1]).view(ctx.x_shape)
         else:

@@ -612,6 +612,22 @@ size_t efg_gemm_bf16x3_wgrad_workspace_bytes(int64_t m, int n, int k);
 int efg_gemm_bf16x3_wgrad_f32(const float* g, int64_t ldg, const float* x, int64_t ldx, int64_t m, int n, int k, float* dw,
                               void* ws, size_t ws_bytes, void* stream);
 
+/* ---- fp32-equivalent split-precision (bf16 x 6) GEMM: EFG_GEMM_ARM=bf16x6, never the default path --------------
+ * The same three products with the same arguments as the bf16 x 3 functions above, every operand split into THREE bf16
+ * pieces (x = p0 + p1 + p2 exactly: all 24 significand bits) and the six leading products p0.p0 + p0.p1 + p1.p0 + p0.p2 +
+ * p1.p1 + p2.p0 accumulated in fp32 on the bf16 MFMA, at 6/16 of the fp32 MFMA time (gemm_bf16x6.hip): the error of an
+ * fp32 product.  An infinite input gives NaN; |x| under about 2^-110 loses its low pieces to bf16 underflow.
+ * `packed` holds efg_gemm_bf16x6_pack_bytes(k, n) bytes (1.5 x the bf16 x 3 size; the two layouts are not interchangeable). */
+size_t efg_gemm_bf16x6_pack_bytes(int k, int n);
+int efg_gemm_bf16x6_pack_f32(const float* w, int64_t stride_k, int64_t stride_n, int k, int n, void* packed,
+                             void* stream);
+int efg_gemm_bf16x6_pack_linear_f32(const float* w, int n_out, int n_in, void* packed_fwd, void* packed_dgrad, void* stream);
+int efg_gemm_bf16x6_f32(const float* a, int64_t m, int k, int64_t lda, const void* packed_b, int n, const float* bias,
+                        int relu, float* c, int64_t ldc, void* stream);
+size_t efg_gemm_bf16x6_wgrad_workspace_bytes(int64_t m, int n, int k);
+int efg_gemm_bf16x6_wgrad_f32(const float* g, int64_t ldg, const float* x, int64_t ldx, int64_t m, int n, int k, float* dw,
+                              void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
