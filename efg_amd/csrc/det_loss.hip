@@ -250,7 +250,10 @@ box_loss_grad_kernel(const float* __restrict__ boxes, const float* __restrict__ 
   for (int k = 0; k < 6; ++k) g[k] = g_l1 * sgn(s[k] - t[k]);
   g[6] = g_rd * sgn(s[6] - t[6]);
   // loss_giou = 1 - giou = 2 - inter/union - union/vol
-  float slo[3], shi[3], tlo[3], thi[3], ik[3], ek[3];
+  // The intersection and enclosing sides are clamp(raw, min = 0), and autograd's clamp passes the gradient for raw >= 0 -- also
+  // at raw == 0 exactly, two boxes that touch on a face (the clamped value alone cannot tell that from separated boxes): the
+  // unclamped differences are kept and tested with >=, as the PyTorch composite (detection3d/losses.py) differentiates.
+  float slo[3], shi[3], tlo[3], thi[3], ik[3], ek[3], iraw[3], eraw[3];
   float inter = 1.f, vol = 1.f, v1 = 1.f, v2 = 1.f;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -260,8 +263,10 @@ box_loss_grad_kernel(const float* __restrict__ boxes, const float* __restrict__ 
     thi[k] = t[k] + 0.5f * t[3 + k];
     v1 *= shi[k] - slo[k];
     v2 *= thi[k] - tlo[k];
-    ik[k] = fmaxf(fminf(shi[k], thi[k]) - fmaxf(slo[k], tlo[k]), 0.f);
-    ek[k] = fmaxf(fmaxf(shi[k], thi[k]) - fminf(slo[k], tlo[k]), 0.f);
+    iraw[k] = fminf(shi[k], thi[k]) - fmaxf(slo[k], tlo[k]);
+    eraw[k] = fmaxf(shi[k], thi[k]) - fminf(slo[k], tlo[k]);
+    ik[k] = fmaxf(iraw[k], 0.f);
+    ek[k] = fmaxf(eraw[k], 0.f);
     inter *= ik[k];
     vol *= ek[k];
   }
@@ -279,13 +284,13 @@ box_loss_grad_kernel(const float* __restrict__ boxes, const float* __restrict__ 
     g_hi += dv1;
     g_lo -= dv1;
     // inter_k = clamp(min(shi, thi) - max(slo, tlo), 0)
-    if (ik[k] > 0.f) {
+    if (iraw[k] >= 0.f) {
       const float di = d_inter * ik[k1] * ik[k2];
       if (shi[k] < thi[k]) g_hi += di; else if (shi[k] == thi[k]) g_hi += 0.5f * di;
       if (slo[k] > tlo[k]) g_lo -= di; else if (slo[k] == tlo[k]) g_lo -= 0.5f * di;
     }
     // enc_k = clamp(max(shi, thi) - min(slo, tlo), 0)
-    if (ek[k] > 0.f) {
+    if (eraw[k] >= 0.f) {
       const float de = d_vol * ek[k1] * ek[k2];
       if (shi[k] > thi[k]) g_hi += de; else if (shi[k] == thi[k]) g_hi += 0.5f * de;
       if (slo[k] < tlo[k]) g_lo -= de; else if (slo[k] == tlo[k]) g_lo -= 0.5f * de;

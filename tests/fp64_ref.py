@@ -1,4 +1,5 @@
-"""Plain float64 references for the sparse convolution and the fused box attention, and an element-wise error bar.
+"""Plain float64 references for the sparse convolution, the fused box attention and the detection-loss tail (matching
+cost, focal loss, box loss), and an element-wise error bar.
 
 Nothing here imports efg_amd.spconv, the oracle or a HIP entry point: the rulebook is rebuilt from the int32 site
 coordinates with torch.sort / searchsorted, the products are torch float64 matmuls, and the box-attention sampling is
@@ -343,3 +344,191 @@ def log_uniform_signed(shape, lo, hi, gen):
     mag = torch.exp(torch.empty(shape, dtype=torch.float64).uniform_(math.log(lo), math.log(hi), generator=gen))
     sign = torch.where(torch.rand(shape, generator=gen) < 0.5, -1.0, 1.0).to(torch.float64)
     return (mag * sign).float()
+
+
+# ---- detection losses: matching cost, focal loss, box loss (csrc/det_loss.hip) -----------------------------------------
+# Written out from the definitions ($CQ/modules/matcher.py:40-80, $CQ/losses.py:26-108, efg/modeling/losses/focal_loss.py);
+# nothing of efg_amd is imported.  Next to every value come `<name>_mag` (the same expression over the absolute values of
+# its terms), `<name>_n` (terms per element) and `<name>_cond`, an ABSOLUTE allowance for assert_elementwise's `geo64`: these
+# formulas are ill-conditioned by construction (1 - p for p near 1, log(1 - p + 1e-8), corners c +- s/2 of a thin box far
+# from the origin), and ANY fp32 evaluation from the fixed fp32 inputs rounds these intermediates.  `cond` is the first-order
+# effect, in float64, of a relative change of 2^-24 in each of them, in whichever direction hurts: sum_v |v * d out / d v|
+# * 2^-24 over the rounded values v that make up p = sigmoid(x) = 1 / (1 + exp(-x)) -- exp(-x), 1 + exp(-x) and the reciprocal:
+# an fp32 sigmoid is three rounded operations, and for p near 1 it is 1.4 x 2^-24 off in torch and in 1 / (1 + expf(-x)) alike
+# --; v = 1 - p; v = p + 1e-8 and 1 - p + 1e-8 (matching cost only); the twelve box corners.  Every v carries a multiplicative
+# leaf (1 + e_v), e_v = 0, and autograd returns d out / d e_v = v * d out / d v with everything computed from v following it.
+# `cond` never sees a kernel's output.
+def _zeros_leaf(like):
+    return torch.zeros_like(like, dtype=torch.float64).requires_grad_(True)
+
+
+def _sigmoid_rounded(x):
+    """sigmoid(x) as 1 / (1 + exp(-x)) with a leaf on each of its three rounded values; returns p and the leaves."""
+    e = [_zeros_leaf(x) for _ in range(3)]
+    return (1 + e[2]) / ((1 + torch.exp(-x) * (1 + e[0])) * (1 + e[1])), e
+
+
+def _sensitivity(out, leaves):
+    """sum over the leaves e of |d out[i] / d e[i, ...]| * 2^-24 for an `out` each of whose elements depends only on the
+    leaves' elements of the same leading index (leaves may carry trailing axes)."""
+    grads = torch.autograd.grad(out.sum(), leaves, retain_graph=True, allow_unused=True)
+    total = torch.zeros_like(out)
+    for g in grads:
+        if g is not None:
+            a = g.detach().abs()
+            total = total + (a.reshape(*out.shape, -1).sum(-1) if a.dim() > out.dim() else a)
+    return total * U32
+
+
+def _box_corners(box):
+    """(lo, hi) [..., 3] of (centre, size) boxes [..., >= 6]."""
+    return box[..., :3] - 0.5 * box[..., 3:6], box[..., :3] + 0.5 * box[..., 3:6]
+
+
+def _giou_parts(vols, inters, encl):
+    """Axis-aligned 3-D IoU and the enclosing-box term of GIoU = iou - (vol - union) / vol, from corner sets (slo, shi, tlo,
+    thi): the two volumes from `vols`, the intersection from `inters`, the enclosing box from `encl` (the same set three
+    times, or three copies that let a caller tell the three paths of a gradient apart).  Returns iou, (vol - union) / vol,
+    (vol + union) / vol."""
+    slo, shi, tlo, thi = vols
+    v1, v2 = (shi - slo).prod(-1), (thi - tlo).prod(-1)
+    slo, shi, tlo, thi = inters
+    inter = (torch.minimum(shi, thi) - torch.maximum(slo, tlo)).clamp(min=0).prod(-1)
+    union = v1 + v2 - inter
+    slo, shi, tlo, thi = encl
+    vol = (torch.maximum(shi, thi) - torch.minimum(slo, tlo)).clamp(min=0).prod(-1)
+    return inter / union, (vol - union) / vol, (vol + union) / vol
+
+
+def match_cost_fp64(logits, boxes, tgt_labels, tgt_boxes, w_class, w_bbox, w_giou, w_rad, alpha=0.25, gamma=2.0):
+    """The matching cost of every (layer, scene, query, target column) in float64.
+
+    logits [L, B, Q, C], boxes [L, B, Q, 7], tgt_labels [B, G] int64, tgt_boxes [B, G, 7].  cost = w_bbox * L1(centre, size) +
+    w_class * (pos - neg) + w_giou * (-GIoU) + w_rad * |d angle|, with p = sigmoid(logit of the column's class), pos =
+    alpha (1 - p)^gamma (-log(p + 1e-8)), neg = (1 - alpha) p^gamma (-log(1 - p + 1e-8)).  Returns a dict: cost [L * B, Q, G],
+    cost_mag (the L1 terms, pos + neg, iou + (vol + union) / vol, under |weights|), cost_n (1) and cost_cond (see above)."""
+    nl, b, q, _ = logits.shape
+    g = tgt_labels.shape[1]
+    lab = tgt_labels.long()[None, :, None, :].expand(nl, b, q, g)
+    x = torch.gather(logits.detach().to(torch.float64), 3, lab)                      # [L, B, Q, G]
+    bx = boxes.detach().to(torch.float64)[:, :, :, None, :].expand(nl, b, q, g, 7)
+    tb = tgt_boxes.detach().to(torch.float64)[None, :, None, :, :].expand(nl, b, q, g, 7)
+    e_q, e_a, e_b = (_zeros_leaf(x) for _ in range(3))
+    p, e_p = _sigmoid_rounded(x)
+    one_m = (1 - p) * (1 + e_q)
+    la, lb = -torch.log((p + 1e-8) * (1 + e_a)), -torch.log((one_m + 1e-8) * (1 + e_b))
+    pos, neg = alpha * one_m ** gamma * la, (1 - alpha) * p ** gamma * lb
+    e_c = [_zeros_leaf(bx[..., :3]) for _ in range(4)]
+    corners = [c * (1 + e) for c, e in zip(_box_corners(bx) + _box_corners(tb), e_c)]
+    iou, enc, enc_mag = _giou_parts(corners, corners, corners)
+    l1 = (bx[..., :6] - tb[..., :6]).abs().sum(-1)
+    rad = (bx[..., 6] - tb[..., 6]).abs()
+    cost = w_bbox * l1 + w_class * (pos - neg) + w_giou * -(iou - enc) + w_rad * rad
+    mag = abs(w_bbox) * l1 + abs(w_class) * (pos.abs() + neg.abs()) + abs(w_giou) * (iou + enc_mag) + abs(w_rad) * rad
+    cond = _sensitivity(cost, e_p + [e_q, e_a, e_b] + e_c)
+    shape = (nl * b, q, g)
+    return dict(cost=cost.detach().reshape(shape), cost_mag=mag.detach().reshape(shape), cost_n=1,
+                cost_cond=cond.reshape(shape))
+
+
+def focal_terms(x, hit, alpha, gamma, p, one_m_p):
+    """The focal loss element and its derivative to the logit as formulas of x, p and the rounded 1 - p: ce = max(x, 0) - x t
+    + log1p(exp(-|x|)), p_t = p t + (1 - p)(1 - t), loss = a_t ce (1 - p_t)^gamma; d ce / dx = p - t, d p_t / dx = +- p (1 - p).
+    Returns loss, the two terms of the derivative."""
+    t = hit.to(x.dtype)
+    ce = x.clamp(min=0) - x * t + torch.log1p(torch.exp(-x.abs()))
+    one_m = torch.where(hit, one_m_p, 1 - one_m_p)          # 1 - p_t
+    a_t = (alpha * t + (1 - alpha) * (1 - t)) if alpha >= 0 else torch.ones_like(t)
+    dpt = torch.where(hit, 1.0, -1.0) * p * one_m_p
+    return a_t * ce * one_m ** gamma, a_t * (p - t) * one_m ** gamma, -a_t * ce * gamma * one_m ** (gamma - 1) * dpt
+
+
+def focal_fp64(logits, tcls, denom, alpha, gamma, grad_out):
+    """Per-layer sums of the sigmoid focal loss against class-index targets (-1: background) and their gradient, float64.
+
+    logits [L, ..., C], tcls int [L, ...], grad_out [L].  Returns loss [L] = sum / denom with loss_mag (= loss: every element
+    is non-negative), loss_n (elements per layer), loss_cond; grad [as logits] from float64 autograd through the definition,
+    grad_mag (|its two terms|), grad_n (1), grad_cond."""
+    nl, c = logits.shape[0], logits.shape[-1]
+    x = logits.detach().to(torch.float64).reshape(nl, -1, c)
+    hit = tcls.reshape(nl, -1, 1).long() == torch.arange(c, device=x.device).view(1, 1, c)
+    go = grad_out.detach().to(torch.float64).reshape(nl, 1, 1) / float(denom)
+    xl = x.clone().requires_grad_(True)
+    pl = torch.sigmoid(xl)
+    loss = focal_terms(xl, hit, alpha, gamma, pl, 1 - pl)[0]
+    grad, = torch.autograd.grad((loss * go).sum(), xl)
+    e_q = _zeros_leaf(x)
+    p, e_p = _sigmoid_rounded(x)
+    val, g1, g2 = focal_terms(x, hit, alpha, gamma, p, (1 - p) * (1 + e_q))
+    per_layer = loss.detach().sum((1, 2)) / float(denom)
+    return dict(loss=per_layer, loss_mag=per_layer.clone(), loss_n=x.shape[1] * c,
+                loss_cond=_sensitivity(val, e_p + [e_q]).sum((1, 2)) / abs(float(denom)),
+                grad=grad.reshape(logits.shape), grad_mag=((g1.abs() + g2.abs()).detach() * go.abs()).reshape(logits.shape),
+                grad_n=1, grad_cond=(_sensitivity(g1 + g2, e_p + [e_q]) * go.abs()).reshape(logits.shape),
+                grad_formula=((g1 + g2).detach() * go).reshape(logits.shape))
+
+
+def box_loss_fp64(boxes, tgt_boxes, l_idx, b_idx, q_idx, g_idx, denom, grad_out):
+    """Per-layer sums of (L1 of centre and size, 1 - GIoU, |d angle|) over matched (prediction, target) pairs, and the
+    gradient to the predicted boxes, in float64.
+
+    boxes [L, B, Q, 7], tgt_boxes [B, G, 7], pair i = prediction (l, b, q)[i] against target (b, g)[i]; pairs with q < 0 or
+    q >= Q are skipped; a (l, b, q) row occurs at most once.  grad_out [L, 3].  The gradient is float64 autograd through
+    abs, minimum / maximum and clamp(min=0), so every tie is autograd's choice: half each at equal corners, the clamp passes at
+    exactly 0, sign(0) = 0.  Returns loss [L, 3] with loss_mag (= loss, the elements are non-negative), loss_n [L, 3] (summed
+    elements: 6 / 1 / 1 per pair), loss_cond; grad [L, B, Q, 7] (zero in unmatched rows) with grad_mag (the L1 sign plus, for
+    GIoU, |the gradient through the two volumes| + |through the intersection| + |through the enclosing box| at each
+    corner), grad_n (1), grad_cond; rows [L, B, Q] bool: the matched rows."""
+    nl, nb, nq = boxes.shape[:3]
+    dev = boxes.device
+    ok = (q_idx >= 0) & (q_idx < nq)
+    li, bi, qi, gi = (t[ok].long() for t in (l_idx, b_idx, q_idx, g_idx))
+    n = li.numel()
+    src = boxes.detach().to(torch.float64)[li, bi, qi]                                 # [n, 7]
+    tgt = tgt_boxes.detach().to(torch.float64)[bi, gi]
+    w = grad_out.detach().to(torch.float64)[li] / float(denom)                        # [n, 3]
+
+    def per_pair(s, sets):
+        iou, enc, _ = _giou_parts(*sets)
+        return torch.stack(((s[:, :6] - tgt[:, :6]).abs().sum(1), 1 - (iou - enc), (s[:, 6] - tgt[:, 6]).abs()), dim=1)
+
+    sl = src.clone().requires_grad_(True)
+    cs = list(_box_corners(sl) + _box_corners(tgt))
+    per = per_pair(sl, (cs, cs, cs))
+    gsrc, = torch.autograd.grad((per * w).sum(), sl) if n else (torch.zeros_like(src),)
+    loss = torch.zeros(nl, 3, dtype=torch.float64, device=dev).index_add_(0, li, per.detach()) / float(denom)
+    count = torch.zeros(nl, dtype=torch.float64, device=dev).index_add_(0, li, torch.ones(n, dtype=torch.float64, device=dev))
+
+    # conditioning and magnitudes: corners c (1 + e); the three paths of the GIoU gradient read their own additive copies
+    e_c = [_zeros_leaf(src[:, :3]) for _ in range(4)]
+    base = [c * (1 + e) for c, e in zip(_box_corners(src) + _box_corners(tgt), e_c)]
+    z = [[_zeros_leaf(src[:, :3]) for _ in range(2)] for _ in range(3)]                # path x (lo, hi) of the prediction
+    sets = [[base[0] + zp[0], base[1] + zp[1], base[2], base[3]] for zp in z]
+    iou, enc, _ = _giou_parts(*sets)
+    gl = 1 - (iou - enc)
+    cond_pair = _sensitivity(gl, e_c) if n else gl.detach()
+    loss_cond = torch.zeros(nl, 3, dtype=torch.float64, device=dev)
+    loss_cond[:, 1] = torch.zeros(nl, dtype=torch.float64, device=dev).index_add_(0, li, cond_pair) / abs(float(denom))
+    g_mag, g_cond = torch.zeros_like(src), torch.zeros_like(src)
+    if n:
+        flat = torch.autograd.grad((gl * w[:, 1]).sum(), [t for zp in z for t in zp], create_graph=True)
+        g_lo, g_hi = flat[0] + flat[2] + flat[4], flat[1] + flat[3] + flat[5]
+        m_lo = sum(flat[i].detach().abs() for i in (0, 2, 4))
+        m_hi = sum(flat[i].detach().abs() for i in (1, 3, 5))
+        sgn_mag = (src - tgt).sign().abs()
+        g_mag[:, :3] = w[:, :1].abs() * sgn_mag[:, :3] + m_hi + m_lo
+        g_mag[:, 3:6] = w[:, :1].abs() * sgn_mag[:, 3:6] + 0.5 * (m_hi + m_lo)
+        g_mag[:, 6] = w[:, 2].abs() * sgn_mag[:, 6]
+        for k in range(3):
+            g_cond[:, k] = _sensitivity((g_hi + g_lo)[:, k], e_c)
+            g_cond[:, 3 + k] = _sensitivity(0.5 * (g_hi - g_lo)[:, k], e_c)
+
+    def rows_of(v):
+        out = torch.zeros(nl, nb, nq, 7, dtype=torch.float64, device=dev)
+        out[li, bi, qi] = v
+        return out
+
+    rows = torch.zeros(nl, nb, nq, dtype=torch.bool, device=dev)
+    rows[li, bi, qi] = True
+    return dict(loss=loss, loss_mag=loss.clone(), loss_n=count.view(nl, 1) * torch.tensor([6.0, 1.0, 1.0], dtype=torch.float64, device=dev),
+                loss_cond=loss_cond, grad=rows_of(gsrc), grad_mag=rows_of(g_mag), grad_n=1, grad_cond=rows_of(g_cond), rows=rows)

@@ -194,3 +194,41 @@ def test_topk_unsorted_is_exact_and_breaks_ties_by_index(n, k):
         assert torch.equal(taken, eq[: taken.numel()])
     v2, i2 = topk_unsorted(x, k)
     assert torch.equal(i2, i) and torch.equal(v2, v)
+
+
+def _topk_reference(x, k):
+    """The documented order in numpy: descending by the sign-magnitude integer image of the float (negative: all bits
+    flipped; otherwise: sign bit set), stable by index; the k first, returned in ascending index order."""
+    bits = x.view(np.uint32)
+    key = np.where(bits & np.uint32(0x80000000), ~bits, bits | np.uint32(0x80000000)).astype(np.int64)
+    idx = np.sort(np.argsort(-key, axis=1, kind="stable")[:, :k], axis=1)
+    return np.take_along_axis(x, idx, axis=1), idx
+
+
+@pytest.mark.parametrize("n,k", [(1, 1), (5, 5), (5, 2), (36864, 1000), (36865, 1000)])
+def test_topk_unsorted_edges_follow_the_integer_image_order(n, k):
+    """Sizes down to one element, k == n, and either side of the staged-LDS limit (36 864 elements); a row of one repeated
+    value, a row with +inf and -inf, and a row whose cut value is 0 with +0.0 and -0.0 both present.  The kernel orders by
+    the integer image of the floats, so -0.0 ranks BELOW +0.0: at a cut of 0 every +0.0 is taken before any -0.0, each group
+    by lowest index (torch.topk, comparing as floats, calls them equal).  Values and indices must equal the numpy
+    restatement of that order bit for bit."""
+    from efg_amd.operators.det_loss import topk_unsorted
+
+    rng = np.random.default_rng(n * 7 + k)
+    x = rng.standard_normal((4, n)).astype(np.float32)
+    x[1] = 0.25
+    some = rng.permutation(n)
+    x[2, some[: max(1, n // 7)]] = np.inf
+    x[2, some[max(1, n // 7): max(1, n // 7) + n // 5]] = -np.inf
+    perm = rng.permutation(n)
+    n_pos = k // 2
+    n_zero = min(n - n_pos, k - n_pos + 3)
+    x[3] = -1.0 - rng.random(n, dtype=np.float32)
+    x[3, perm[:n_pos]] = 1.0 + rng.random(n_pos, dtype=np.float32)
+    x[3, perm[n_pos:n_pos + n_zero]] = np.where(rng.random(n_zero) < 0.5, np.float32(-0.0), np.float32(0.0))
+    if n_zero >= 2:
+        x[3, perm[n_pos]], x[3, perm[n_pos + 1]] = np.float32(-0.0), np.float32(0.0)
+    want_v, want_i = _topk_reference(x, k)
+    v, i = topk_unsorted(torch.from_numpy(x).cuda(), k)
+    assert np.array_equal(i.cpu().numpy(), want_i)
+    assert np.array_equal(v.cpu().numpy().view(np.int32), want_v.view(np.int32))
