@@ -132,25 +132,22 @@ _SIGS = {
                            [c_size_t, c_void_p]),
     "efg_gn_backward_f32": (c_int, [c_void_p] * 5 + [c_int, c_int64, c_int, c_int] + [c_void_p] * 4 +
                             [c_size_t, c_void_p]),
-    "efg_gemm_bf16x3_pack_bytes": (c_size_t, [c_int, c_int]),
-    "efg_gemm_bf16x3_pack_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "efg_gemm_bf16x3_pack_linear_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "efg_gemm_bf16x3_f32": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64,
-                                    c_void_p]),
-    "efg_gemm_bf16x3_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
-    "efg_gemm_bf16x3_wgrad_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
-                                          c_size_t, c_void_p]),
-    "efg_gemm_bf16x6_pack_bytes": (c_size_t, [c_int, c_int]),
-    "efg_gemm_bf16x6_pack_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p]),
-    "efg_gemm_bf16x6_pack_linear_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "efg_gemm_bf16x6_f32": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64,
-                                    c_void_p]),
-    "efg_gemm_bf16x6_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
-    "efg_gemm_bf16x6_wgrad_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
-                                          c_size_t, c_void_p]),
     "efg_colsum_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "efg_colsum_f32": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
+
+# the split-precision GEMM arms (csrc/gemm_split_bf16.h): one set of six signatures under two prefixes
+_GEMM_SPLIT_SIGS = {
+    "_pack_bytes": (c_size_t, [c_int, c_int]),
+    "_pack_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "_pack_linear_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "_f32": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "_wgrad_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                           c_void_p]),
+}
+for _prefix in ("efg_gemm_bf16x3", "efg_gemm_bf16x6"):
+    _SIGS.update({_prefix + _name: _sig for _name, _sig in _GEMM_SPLIT_SIGS.items()})
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

@@ -116,7 +116,7 @@ def usable(layer, src, pos, ref_windows):
     fused sampling kernel applicable, exact-fp32 products (the bf16x3 / bf16x6 arms keep the module-by-module form)."""
     attn = layer.self_attn
     return (_ENABLED and src.is_cuda and src.dtype == torch.float32 and torch.is_grad_enabled() and src.dim() == 3
-            and not (_lin._ARM_BF16X3 or _lin._ARM_BF16X6) and os.environ.get("EFG_FUSED_LINEAR", "1") != "0"
+            and _lin.arm_active() is None and os.environ.get("EFG_FUSED_LINEAR", "1") != "0"
             and os.environ.get("EFG_FUSED_LN", "1") != "0" and _baf.FUSED_ENABLED
             and not (layer.training and (layer.dropout.p > 0 or layer.dropout1.p > 0 or layer.dropout2.p > 0))
             and attn.head_dim == 32 and attn.num_level * attn.num_point <= 32 and not ref_windows.requires_grad

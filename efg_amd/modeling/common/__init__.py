@@ -61,7 +61,7 @@ class Conv2d(nn.Conv2d):
             x = conv3x3(x, self.weight, self.bias)   # EFG_DETERMINISTIC=1: the layer off MIOpen, as fixed-order GEMMs
         elif (x.is_cuda and self.kernel_size == (3, 3) and self.stride == (1, 1) and self.padding == (1, 1)
               and self.dilation == (1, 1) and self.groups == 1 and torch.is_grad_enabled()
-              and (_linear_mod._ARM_BF16X3 or _linear_mod._ARM_BF16X6)
+              and _linear_mod.arm_active() is not None
               and os.environ.get("EFG_CONV2D_ARM", "1") != "0" and arm_covers(x, self.weight)):
             x = conv3x3_arm(x, self.weight, self.bias)   # the split-precision A/B arm (never the default)
         else:

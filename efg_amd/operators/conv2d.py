@@ -116,10 +116,7 @@ def _tap_rows(buf, start_row, rows, c):
 def _arm_products():
     """operators/gemm_bf16x6.py when the x6 arm alone is switched on, else operators/gemm_bf16x3.py (also with no switch set:
     conv3x3_arm called by hand is the x3 arm, as it was before there were two)."""
-    G = arm_module()
-    if G is None:
-        from . import gemm_bf16x3 as G
-    return G
+    return arm_module(default="bf16x3")
 
 
 class Conv3x3ArmFunction(Function):

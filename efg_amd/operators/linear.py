@@ -7,6 +7,7 @@ gradient of the 70 688-row encoder layers is computed as 16 row chunks in one ba
 70 688-token encoder sequence and at 15 us apiece on the decoder's few thousand rows (1.7 ms per step together).
 Same parameters and state-dict names as nn.Linear ($CQ/transformer.py:215-243,273-317, $CQ/modules/blocks.py:5-17,
 $CQ/modules/box_attention.py:31-40)."""
+import importlib
 import os
 
 import torch
@@ -57,8 +58,8 @@ _SMALL_FUSED = True
 
 
 # The A/B arm of the bench (EFG_GEMM_ARM=bf16x3, never the default): forward and data-gradient products of the long
-# matrices, and their weight gradients, as three bf16 MFMA products of split operands (csrc/gemm_bf16x3.hip).  The bias
-# gradient and every short matrix stay exact fp32.
+# matrices, and their weight gradients, as three bf16 MFMA products of operands split into two pieces
+# (csrc/gemm_bf16x3.hip).  The bias gradient and every short matrix stay exact fp32.
 _ARM_BF16X3 = os.environ.get("EFG_GEMM_ARM", "") == "bf16x3"
 # (No cache of the split weights across calls: one keyed on the parameter's `_version` went stale -- the fused AdamW step
 # updates parameters without moving it; tests/test_gemm_bf16x3_gpu.py::test_split_weights_follow_the_optimizer.  The
@@ -66,29 +67,30 @@ _ARM_BF16X3 = os.environ.get("EFG_GEMM_ARM", "") == "bf16x3"
 
 
 # The fp32-equivalent arm (EFG_GEMM_ARM=bf16x6, never the default either): the same products of the same shapes as six
-# bf16 MFMA products of operands split into three pieces (csrc/gemm_bf16x6.hip) -- the error of an fp32 product.  With both
-# switches on, x3 wins: the bench's own arm leg sets _ARM_BF16X3 and keeps measuring what it measures.
+# bf16 MFMA products of operands split into three pieces (csrc/gemm_bf16x6.hip, the same source with one more piece) -- the
+# error of an fp32 product.
 _ARM_BF16X6 = os.environ.get("EFG_GEMM_ARM", "") == "bf16x6"
 
 
-def arm_module():
-    """The module of split products the switches select (read at call time: tests and the bench flip them), None with both off."""
-    if _ARM_BF16X3:
-        from . import gemm_bf16x3 as G
+def arm_active():
+    """"bf16x3", "bf16x6" or None: the arm the two switches select.  The one place that reads them, at call time (tests and
+    the bench flip them).  With both on, x3 wins: the bench's own arm leg sets _ARM_BF16X3 and keeps measuring what it
+    measures."""
+    return "bf16x3" if _ARM_BF16X3 else "bf16x6" if _ARM_BF16X6 else None
 
-        return G
-    if _ARM_BF16X6:
-        from . import gemm_bf16x6 as G
 
-        return G
-    return None
+def arm_module(default=None):
+    """The module of split products of the active arm (operators/gemm_bf16x3.py or gemm_bf16x6.py); with both switches off
+    that of the arm `default`, or None."""
+    arm = arm_active() or default
+    return importlib.import_module(".gemm_" + arm, __package__) if arm else None
 
 
 def _arm_ok(a2, min_cols=64):
     """a2: the [rows, K] operand of a product: the long matrices only (the decoder-sized Linear + ReLU layers also come
     through LinearFunction since round 4 and stay exact fp32).  Below K = 64 the split product loses to fp32 (op bench: 32 -> 256 29.6 vs
     26.2 us; the 32-row weight gradient 44.5 vs 28.5 us)."""
-    return ((_ARM_BF16X3 or _ARM_BF16X6) and a2.dim() == 2 and a2.stride(1) == 1 and a2.shape[1] % 4 == 0
+    return (arm_active() is not None and a2.dim() == 2 and a2.stride(1) == 1 and a2.shape[1] % 4 == 0
             and a2.stride(0) % 4 == 0 and a2.data_ptr() % 16 == 0 and a2.shape[0] >= _FUSED_MIN_ROWS
             and a2.shape[1] >= min_cols)
 
@@ -106,7 +108,7 @@ _X6_MIN_K = 256
 
 def _arm_gemm(a2):
     """The module whose `gemm` takes the product of a2 [rows, K] with a [K, N] weight, or None for the library."""
-    if not _arm_ok(a2) or (not _ARM_BF16X3 and a2.shape[1] < _X6_MIN_K):
+    if not _arm_ok(a2) or (arm_active() == "bf16x6" and a2.shape[1] < _X6_MIN_K):
         return None
     return arm_module()
 

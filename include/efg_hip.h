@@ -591,7 +591,7 @@ int efg_relu_bwd_colsum_f32(const float* g, const float* y, int64_t rows, int co
 /* ---- split-precision (bf16 x 3) GEMM: the A/B arm of the bench, never the default path ---------------------
  * C[m, n] = A[m, k] . B[k, n] (+ bias[n]) (ReLU if relu != 0), fp32 in and out, every operand split into two bf16 terms
  * (x = hi + lo) and hi.hi + hi.lo + lo.hi accumulated in fp32 on the bf16 MFMA: ~2^-16 relative per product instead of
- * fp32's 2^-24, at 3/16 of the fp32 MFMA time (gemm_bf16x3.hip).  Stands where the encoder's nn.Linear products
+ * fp32's 2^-24, at 3/16 of the fp32 MFMA time (gemm_bf16x3.hip, one of the two instantiations of gemm_split_bf16.h).  Stands where the encoder's nn.Linear products
  * ($CQ/transformer.py:215-243, $CQ/modules/box_attention.py:31-40) call hipBLASLt in fp32 when EFG_GEMM_ARM=bf16x3.
  *   pack: B(kk, nn) = w[kk * stride_k + nn * stride_n] (so a Linear weight [out, in] packs as B = W^T with
  *         stride_k = 1, stride_n = in, and as B = W with stride_k = in, stride_n = 1), split and laid out in the
@@ -615,7 +615,7 @@ int efg_gemm_bf16x3_wgrad_f32(const float* g, int64_t ldg, const float* x, int64
 /* ---- fp32-equivalent split-precision (bf16 x 6) GEMM: EFG_GEMM_ARM=bf16x6, never the default path --------------
  * The same three products with the same arguments as the bf16 x 3 functions above, every operand split into THREE bf16
  * pieces (x = p0 + p1 + p2 exactly: all 24 significand bits) and the six leading products p0.p0 + p0.p1 + p1.p0 + p0.p2 +
- * p1.p1 + p2.p0 accumulated in fp32 on the bf16 MFMA, at 6/16 of the fp32 MFMA time (gemm_bf16x6.hip): the error of an
+ * p1.p1 + p2.p0 accumulated in fp32 on the bf16 MFMA, at 6/16 of the fp32 MFMA time (gemm_bf16x6.hip, the other instantiation): the error of an
  * fp32 product.  An infinite input gives NaN; |x| under about 2^-110 loses its low pieces to bf16 underflow.
  * `packed` holds efg_gemm_bf16x6_pack_bytes(k, n) bytes (1.5 x the bf16 x 3 size; the two layouts are not interchangeable). */
 size_t efg_gemm_bf16x6_pack_bytes(int k, int n);
