@@ -105,7 +105,8 @@ def to_attr(x):
 # efg/config/default.yaml:1-66, the keys this package (or a reference YAML's interpolation) reads
 _DEFAULTS = {
     "task": "train",
-    "model": {"device": "cuda", "weights": ""},
+    # (loss.giou_type -- this package's own key: "aligned" | "rotated", detection3d/heads.py)
+    "model": {"device": "cuda", "weights": "", "loss": {"giou_type": "aligned"}},
     "dataloader": {"num_workers": 2, "batch_size": 16},
     "ddp": {"backend": "nccl", "num_gpus": 1, "num_machines": 1, "machine_rank": 0, "find_unused_parameters": False},
     "solver": {"lr_scheduler": {"max_epochs": None, "max_iters": None}, "optimizer": {"lr": None},

@@ -6,7 +6,8 @@ from torch import nn
 
 from .losses import Det3DLoss
 from .matcher import HungarianMatcher3d
-from ..operators.det_loss import box_refine
+from ..operators.det_loss import GIOU_TYPES, box_refine
+from ..operators.rot_giou import code_frame
 from .utils import MLP, get_clones
 
 
@@ -31,11 +32,21 @@ class Det3DHead(nn.Module):
         self.class_embed = get_clones(class_embed, num_layers)
         self.bbox_embed = get_clones(bbox_embed, num_layers)
         mc = config.model.loss.matcher
+        # model.loss.giou_type: "aligned" (the reference's axis-aligned GIoU) | "rotated" (heading-aware, csrc/rot_giou.hip),
+        # for the matching cost and loss_giou alike; the rotated one reads the box codes through the box coder's frame
+        giou_type = config.model.loss.get("giou_type", "aligned")
+        if giou_type not in GIOU_TYPES:
+            raise ValueError("model.loss.giou_type must be one of %s, got %r" % (" | ".join(GIOU_TYPES), giou_type))
+        frame = None
+        if giou_type == "rotated":
+            pc_range = [float(v) for v in config.dataset.pc_range]
+            frame = code_frame(pc_range[3] - pc_range[0], pc_range[4] - pc_range[1])   # VoxelBoxCoder3D.pc_size[:2]
         matcher = HungarianMatcher3d(cost_class=mc.class_weight, cost_bbox=mc.bbox_weight, cost_giou=mc.giou_weight,
-                                     cost_rad=mc.rad_weight)
+                                     cost_rad=mc.rad_weight, giou_type=giou_type, frame=frame)
         weight_dict = {"loss_ce": config.model.loss.class_loss_coef, "loss_bbox": config.model.loss.bbox_loss_coef,
                        "loss_giou": config.model.loss.giou_loss_coef, "loss_rad": config.model.loss.rad_loss_coef}
-        self.losses = Det3DLoss(matcher=matcher, weight_dict=weight_dict, losses=["focal_labels", "boxes"])
+        self.losses = Det3DLoss(matcher=matcher, weight_dict=weight_dict, losses=["focal_labels", "boxes"],
+                                giou_type=giou_type, frame=frame)
         if with_aux:
             aux = {k + "_enc_0": v for k, v in self.losses.weight_dict.items()}
             for i in range(config.model.transformer.dec_layers - 1):

@@ -14,8 +14,8 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from ..operators.det_loss import BoxLossLayers, FocalLossLayers, device_scalar
-from .utils import box_cxcyczlwh_to_xyxyxy, paired_box3d_giou, sigmoid_focal_loss
+from ..operators.det_loss import BoxLossLayers, BoxLossRotLayers, FocalLossLayers, check_giou_type, device_scalar
+from .utils import box_cxcyczlwh_to_xyxyxy, paired_box3d_giou, paired_rot_giou3d, sigmoid_focal_loss
 
 
 def get_world_size():
@@ -114,7 +114,8 @@ def match_together(calls, side=None):
         off = 0
         for (matcher, pr), n in zip(calls, sizes):
             match_cost(pr["m_logits"], pr["m_boxes"], pr["tgt_labels"], pr["tgt_boxes"], matcher.cost_class, matcher.cost_bbox,
-                       matcher.cost_giou, matcher.cost_rad, out=cost[off:off + n])
+                       matcher.cost_giou, matcher.cost_rad, out=cost[off:off + n], giou_type=matcher.giou_type,
+                       frame=matcher.frame)
             off += n
         assigned = linear_sum_assignment_batched(cost, ng_dev)
     if side is not None:
@@ -130,8 +131,12 @@ def match_together(calls, side=None):
 class Det3DLoss(nn.Module):
     """$CQ/losses.py:111-214 (+ ClassificationLoss :26-73, RegressionLoss :76-108)."""
 
-    def __init__(self, matcher, weight_dict, losses, focal_alpha=0.25):
+    def __init__(self, matcher, weight_dict, losses, focal_alpha=0.25, giou_type="aligned", frame=None):
+        """giou_type "rotated": loss_giou is 1 - the heading-aware GIoU of the boxes read through `frame` = (sx, sy, yaw_scale,
+        yaw_offset); "aligned" (the reference's): axis-aligned."""
         super().__init__()
+        check_giou_type(giou_type, frame)
+        self.giou_type, self.frame = giou_type, (tuple(float(v) for v in frame) if frame is not None else None)
         self.matcher, self.weight_dict, self.losses = matcher, weight_dict, losses
         for loss in losses:
             if loss not in ("boxes", "focal_labels"):
@@ -162,7 +167,10 @@ class Det3DLoss(nn.Module):
                 tcls.index_put_((l_idx, b_idx, q_idx), cls.to(torch.int32))
                 out["loss_ce"] = FocalLossLayers.apply(logits, tcls, denom, self.focal_alpha, 2.0)
             if want_box:
-                sums = BoxLossLayers.apply(boxes, tgt_boxes, l_idx, b_idx, q_idx, g_idx, denom)   # [L, 3]
+                if self.giou_type == "rotated":
+                    sums = BoxLossRotLayers.apply(boxes, tgt_boxes, l_idx, b_idx, q_idx, g_idx, denom, self.frame)
+                else:
+                    sums = BoxLossLayers.apply(boxes, tgt_boxes, l_idx, b_idx, q_idx, g_idx, denom)   # [L, 3]
                 # the three families as ONE family-major [3 L] vector under a joint key: three column selects would put
                 # three SelectBackward nodes (zero-fill + copy + add each) into the graph, three times per step
                 out["loss_bbox|loss_giou|loss_rad"] = sums.t().reshape(-1)
@@ -177,7 +185,10 @@ class Det3DLoss(nn.Module):
             src = boxes[l_idx, b_idx, q_idx]
             tgt = tgt_boxes[b_idx, g_idx]
             l1 = F.l1_loss(src, tgt, reduction="none")
-            giou = 1 - paired_box3d_giou(box_cxcyczlwh_to_xyxyxy(src[:, :6]), box_cxcyczlwh_to_xyxyxy(tgt[:, :6]))
+            if self.giou_type == "rotated":
+                giou = 1 - paired_rot_giou3d(src, tgt, self.frame)
+            else:
+                giou = 1 - paired_box3d_giou(box_cxcyczlwh_to_xyxyxy(src[:, :6]), box_cxcyczlwh_to_xyxyxy(tgt[:, :6]))
             per = torch.stack((l1[:, :6].sum(1), giou, l1[:, 6:].sum(1)), dim=1)  # [n, 3]
             sums = per.new_zeros(n_layers, 3).index_add_(0, l_idx, per) / num_boxes
             out["loss_bbox"], out["loss_giou"], out["loss_rad"] = sums[:, 0], sums[:, 1], sums[:, 2]

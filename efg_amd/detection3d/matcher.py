@@ -7,13 +7,17 @@ from scipy.optimize import linear_sum_assignment
 from torch import nn
 
 from ..operators.assignment import linear_sum_assignment_batched
-from ..operators.det_loss import match_cost
-from .utils import box_cxcyczlwh_to_xyxyxy, generalized_box3d_iou, pairwise_box3d_giou
+from ..operators.det_loss import check_giou_type, match_cost
+from .utils import box_cxcyczlwh_to_xyxyxy, generalized_box3d_iou, pairwise_box3d_giou, pairwise_rot_giou3d
 
 
 class HungarianMatcher3d(nn.Module):
-    def __init__(self, cost_class=1.0, cost_bbox=1.0, cost_giou=1.0, cost_rad=1.0):
+    def __init__(self, cost_class=1.0, cost_bbox=1.0, cost_giou=1.0, cost_rad=1.0, giou_type="aligned", frame=None):
+        """giou_type "rotated": the GIoU term is the heading-aware one of the boxes read through `frame` = (sx, sy, yaw_scale,
+        yaw_offset) (utils.rot_giou3d); "aligned" (the reference's): axis-aligned, the heading ignored."""
         super().__init__()
+        check_giou_type(giou_type, frame)
+        self.giou_type, self.frame = giou_type, (tuple(float(v) for v in frame) if frame is not None else None)
         self.cost_class, self.cost_bbox, self.cost_giou, self.cost_rad = cost_class, cost_bbox, cost_giou, cost_rad
         assert cost_class != 0 or cost_bbox != 0 or cost_giou != 0 or cost_rad != 0, "all costs cant be 0"
 
@@ -36,7 +40,10 @@ class HungarianMatcher3d(nn.Module):
             tgt_ids = targets[i]["labels"]
             tgt_bbox = targets[i]["gt_boxes"][..., :6].float()
             tgt_rad = targets[i]["gt_boxes"][..., 6:].float()
-            cost_giou = -generalized_box3d_iou(box_cxcyczlwh_to_xyxyxy(out_bbox[i]), box_cxcyczlwh_to_xyxyxy(tgt_bbox))
+            if self.giou_type == "rotated":
+                cost_giou = -pairwise_rot_giou3d(pred_boxes[i].float(), targets[i]["gt_boxes"].float(), self.frame)
+            else:
+                cost_giou = -generalized_box3d_iou(box_cxcyczlwh_to_xyxyxy(out_bbox[i]), box_cxcyczlwh_to_xyxyxy(tgt_bbox))
             cost_class = pos_cost[i][:, tgt_ids] - neg_cost[i][:, tgt_ids]
             cost_bbox = torch.cdist(out_bbox[i], tgt_bbox, p=1)
             cost_rad = torch.cdist(out_rad[i], tgt_rad, p=1)
@@ -56,7 +63,7 @@ class HungarianMatcher3d(nn.Module):
         g = tgt_labels.shape[1]
         if logits.is_cuda:  # cost in one kernel (csrc/det_loss.hip), assignment on the device (csrc/matcher.hip)
             cost = match_cost(logits, boxes, tgt_labels, tgt_boxes, self.cost_class, self.cost_bbox, self.cost_giou,
-                              self.cost_rad)
+                              self.cost_rad, giou_type=self.giou_type, frame=self.frame)
             ng = torch.tensor(list(counts) * n_layers, dtype=torch.int32).to(cost.device, non_blocking=True)
             return linear_sum_assignment_batched(cost, ng).view(n_layers, bs, g)
         out_prob = logits.sigmoid().float()
@@ -69,7 +76,10 @@ class HungarianMatcher3d(nn.Module):
         tb, tr = tgt_boxes[..., :6].float(), tgt_boxes[..., 6:].float()
         cost_bbox = (out_bbox[:, :, :, None, :] - tb[None, :, None, :, :]).abs().sum(-1)
         cost_rad = (out_rad[:, :, :, None, :] - tr[None, :, None, :, :]).abs().sum(-1)
-        cost_giou = -pairwise_box3d_giou(box_cxcyczlwh_to_xyxyxy(out_bbox), box_cxcyczlwh_to_xyxyxy(tb)[None])
+        if self.giou_type == "rotated":
+            cost_giou = -pairwise_rot_giou3d(boxes.float(), tgt_boxes.float()[None], self.frame)
+        else:
+            cost_giou = -pairwise_box3d_giou(box_cxcyczlwh_to_xyxyxy(out_bbox), box_cxcyczlwh_to_xyxyxy(tb)[None])
         cost = (self.cost_bbox * cost_bbox + self.cost_class * cost_class + self.cost_giou * cost_giou +
                 self.cost_rad * cost_rad)
         host = cost.numpy()

@@ -7,6 +7,17 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
+from .rot_giou import frame_arg
+
+GIOU_TYPES = ("aligned", "rotated")
+
+
+def check_giou_type(giou_type, frame):
+    """"aligned": axis-aligned 3-D GIoU (heading ignored); "rotated": heading-aware, which needs the boxes' frame."""
+    if giou_type not in GIOU_TYPES:
+        raise ValueError("giou_type must be one of %s, got %r" % (" | ".join(GIOU_TYPES), giou_type))
+    if giou_type == "rotated" and (frame is None or len(frame) != 4):
+        raise ValueError("giou_type 'rotated' needs frame = (sx, sy, yaw_scale, yaw_offset), got %r" % (frame,))
 
 
 def device_scalar(value, device):
@@ -16,15 +27,24 @@ def device_scalar(value, device):
     return torch.tensor(float(value), dtype=torch.float32).to(device, non_blocking=True)
 
 
-def match_cost(logits, boxes, tgt_labels, tgt_boxes, w_class, w_bbox, w_giou, w_rad, alpha=0.25, gamma=2.0, out=None):
+def match_cost(logits, boxes, tgt_labels, tgt_boxes, w_class, w_bbox, w_giou, w_rad, alpha=0.25, gamma=2.0, out=None,
+               giou_type="aligned", frame=None):
     """logits [L,B,Q,C], boxes [L,B,Q,7], tgt_labels [B,G] int64, tgt_boxes [B,G,7] -> cost [L*B, Q, G] (into `out`, a
-    contiguous [L*B, Q, G] fp32 view, if given)."""
+    contiguous [L*B, Q, G] fp32 view, if given).  giou_type "rotated": the heading-aware GIoU (csrc/rot_giou.hip) of the boxes
+    read through `frame` = (sx, sy, yaw_scale, yaw_offset) in place of the axis-aligned one."""
+    check_giou_type(giou_type, frame)
     L.require_gpu(logits, boxes, tgt_labels, tgt_boxes)
     n_layers, b, q, c = logits.shape
     g = tgt_labels.shape[1]
     lg, bx = logits.detach().contiguous().float(), boxes.detach().contiguous().float()
     cost = out if out is not None else torch.empty((n_layers * b, q, g), dtype=torch.float32, device=logits.device)
     assert cost.shape == (n_layers * b, q, g) and cost.dtype == torch.float32 and cost.is_contiguous()
+    if giou_type == "rotated":
+        L.check(L.lib().efg_match_cost_rot_f32(L.ptr(lg), L.ptr(bx), L.ptr(tgt_labels.contiguous()),
+                                               L.ptr(tgt_boxes.contiguous().float()), n_layers * b, b, q, c, g, float(w_class),
+                                               float(w_bbox), float(w_giou), float(w_rad), float(alpha), float(gamma),
+                                               frame_arg(frame), L.ptr(cost), L.stream()))
+        return cost
     L.check(L.lib().efg_match_cost_f32(L.ptr(lg), L.ptr(bx), L.ptr(tgt_labels.contiguous()),
                                        L.ptr(tgt_boxes.contiguous().float()), n_layers * b, b, q, c, g, float(w_class),
                                        float(w_bbox), float(w_giou), float(w_rad), float(alpha), float(gamma),
@@ -85,6 +105,37 @@ class BoxLossLayers(Function):
                                                   L.ptr(g_idx), l_idx.numel(), n_layers, b, q, tb.shape[1], L.ptr(denom),
                                                   L.ptr(grad_out.contiguous()), L.ptr(grad), L.stream()))
         return grad, None, None, None, None, None, None
+
+
+class BoxLossRotLayers(Function):
+    """BoxLossLayers with the heading-aware GIoU in column 1: boxes [L,B,Q,7], tgt_boxes [B,G,7], pair indices, denom, frame
+    (sx, sy, yaw_scale, yaw_offset) -> [L, 3] (bbox L1, 1 - rotated GIoU, rad L1) sums / denom."""
+
+    @staticmethod
+    def forward(ctx, boxes, tgt_boxes, l_idx, b_idx, q_idx, g_idx, denom, frame):
+        n_layers, b, q = boxes.shape[:3]
+        g = tgt_boxes.shape[1]
+        bx, tb = boxes.contiguous(), tgt_boxes.contiguous()
+        idx = [t.contiguous() for t in (l_idx, b_idx, q_idx, g_idx)]
+        n = idx[0].numel()
+        out = torch.empty((n_layers, 3), dtype=torch.float32, device=boxes.device)
+        L.check(L.lib().efg_box_loss_rot_forward_f32(L.ptr(bx), L.ptr(tb), *[L.ptr(t) for t in idx], n, n_layers, b, q, g,
+                                                     L.ptr(denom), frame_arg(frame), L.ptr(out), L.stream()))
+        ctx.save_for_backward(bx, tb, *idx, denom)
+        ctx.frame = tuple(float(v) for v in frame)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        bx, tb, l_idx, b_idx, q_idx, g_idx, denom = ctx.saved_tensors
+        n_layers, b, q = bx.shape[:3]
+        grad = torch.zeros_like(bx)
+        L.check(L.lib().efg_box_loss_rot_backward_f32(L.ptr(bx), L.ptr(tb), L.ptr(l_idx), L.ptr(b_idx), L.ptr(q_idx),
+                                                      L.ptr(g_idx), l_idx.numel(), n_layers, b, q, tb.shape[1], L.ptr(denom),
+                                                      L.ptr(grad_out.contiguous()), frame_arg(ctx.frame), L.ptr(grad),
+                                                      L.stream()))
+        return grad, None, None, None, None, None, None, None
 
 
 class BoxRefineFunction(Function):

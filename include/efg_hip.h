@@ -529,6 +529,29 @@ int efg_box_loss_backward_f32(const float* boxes, const float* tgt_boxes, const 
                               const int64_t* q_idx, const int64_t* g_idx, int64_t n, int layers, int b, int q, int g,
                               const float* denom, const float* grad_out, float* grad_boxes, void* stream);
 
+/* Heading-aware 3-D GIoU of (cx, cy, cz, l, w, h, rad) boxes (csrc/rot_giou.hip): rotated-rectangle intersection and convex
+ * hull in the bird's-eye view times the z overlap / z range.  `frame` is a HOST array of four floats (sx, sy, yaw_scale,
+ * yaw_offset): metric centre (cx sx, cy sy), size (l sx, w sy), yaw = rad yaw_scale + yaw_offset -- (pc_size_x, pc_size_y,
+ * 2 pi, -pi) for the ConQueR codes, (1, 1, 1, 0) for metric boxes.
+ * paired: a, b f32 [n, 7] -> giou [n], iou [n] (optional, NULL); backward: grad_a, grad_b (optional, NULL) [n, 7] =
+ * grad_giou[i] * d giou / d box, plain stores.  n == 0 returns without a launch. */
+int efg_rot_giou_paired_forward_f32(const float* a, const float* b, int64_t n, const float* frame, float* giou, float* iou,
+                                    void* stream);
+int efg_rot_giou_paired_backward_f32(const float* a, const float* b, int64_t n, const float* frame, const float* grad_giou,
+                                     float* grad_a, float* grad_b, void* stream);
+/* efg_match_cost_f32 / efg_box_loss_*_f32 with the rotated GIoU in place of the axis-aligned one (every other term and the
+ * per-layer reduction as there). */
+int efg_match_cost_rot_f32(const float* logits, const float* boxes, const int64_t* tgt_labels, const float* tgt_boxes,
+                           int p, int b, int q, int c, int g, float w_class, float w_bbox, float w_giou, float w_rad,
+                           float alpha, float gamma, const float* frame, float* cost, void* stream);
+int efg_box_loss_rot_forward_f32(const float* boxes, const float* tgt_boxes, const int64_t* l_idx, const int64_t* b_idx,
+                                 const int64_t* q_idx, const int64_t* g_idx, int64_t n, int layers, int b, int q, int g,
+                                 const float* denom, const float* frame, float* out, void* stream);
+int efg_box_loss_rot_backward_f32(const float* boxes, const float* tgt_boxes, const int64_t* l_idx, const int64_t* b_idx,
+                                  const int64_t* q_idx, const int64_t* g_idx, int64_t n, int layers, int b, int q, int g,
+                                  const float* denom, const float* grad_out, const float* frame, float* grad_boxes,
+                                  void* stream);
+
 /* Unsorted top-k per row of x [rows, n] (the proposal selection, $CQ/transformer.py:65: torch.topk(sorted=False)):
  * values [rows, k], indices int64 [rows, k], in ascending index order; of the elements equal to the k-th largest value
  * the lowest indices are taken (a fixed rule: two runs pick the same proposals).  One launch, one workgroup per row. */
