@@ -139,6 +139,11 @@ _SIGS = {
                             [c_size_t, c_void_p]),
     "efg_colsum_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "efg_colsum_f32": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "efg_det_eval_max_pred": (c_int, []),
+    "efg_det_eval_max_gt": (c_int, []),
+    "efg_det_eval_pair_weights_f32": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_float] * 3 + [c_void_p, c_void_p]),
+    "efg_det_eval_assign_f32": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p] * 7),
+    "efg_det_eval_accumulate": (c_int, [c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 3),
 }
 
 # the split-precision GEMM arms (csrc/gemm_split_bf16.h): one set of six signatures under two prefixes

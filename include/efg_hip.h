@@ -651,6 +651,38 @@ size_t efg_gemm_bf16x6_wgrad_workspace_bytes(int64_t m, int n, int k);
 int efg_gemm_bf16x6_wgrad_f32(const float* g, int64_t ldg, const float* x, int64_t ldx, int64_t m, int n, int k, float* dw,
                               void* ws, size_t ws_bytes, void* stream);
 
+/* ---- detection evaluation: Waymo-protocol AP / APH counts (det_eval.hip, DESIGN.md "Detection evaluation") ----
+ * Frame-segmented (CSR) layout: the predictions and ground truths of the n_frames frames of one call are concatenated,
+ * frame f owning rows pred_off[f]..pred_off[f+1] and gt_off[f]..gt_off[f+1] (int32 [n_frames + 1]) and the dense
+ * P_f x G_f weight block at weights + blk_off[f] (int64 [n_frames], row stride G_f).  Boxes are [n, 7] (x, y, z, l, w, h,
+ * yaw); labels are 1 = vehicle, 2 = pedestrian, 3 = cyclist.
+ *   pair_weights: weight = 3-D IoU (the arithmetic of efg_boxes_bev_f32 mode 2, bit for bit) where the labels are equal,
+ *     in 1..3, and the IoU is finite and >= the class threshold; exactly 0 elsewhere.  max_pred / max_gt: the largest
+ *     P_f / G_f of the call (grid size).
+ *   assign: one problem per row of `problems` (int32 [n_problems, 6]: frame, first prediction, predictions, first ground
+ *     truth, ground truths, class 0..2; the ranges are global indices inside the frame's ranges).  The predictions of a
+ *     problem are sorted by descending score (scores [sum P], fp32).  For each of the 101 score cutoffs float(0.01 k),
+ *     k < 100, and 1.0 the kernel writes the counts of the maximum-weight assignment between the predictions with
+ *     score >= cutoff and the ground truths: counts int32 [n_problems, 101, 5] = (tp at level 1, tp at level 2, unmatched
+ *     predictions, unmatched ground truths of level <= 1, of level <= 2) and sums fp64 [n_problems, 101, 3] = (heading
+ *     accuracy of the level-1 true positives, of the level-2 ones, matched weight).  gt_level int32 [sum G]: difficulty.
+ *     max_pred / max_gt: the largest problem of the call; more than efg_det_eval_max_pred() predictions or
+ *     efg_det_eval_max_gt() ground truths in one problem is an error, nothing is truncated.
+ *   accumulate: total_counts int64 [3, 101, 5] and total_sums fp64 [3, 101, 3] += the problems of each class, in problem
+ *     order (no atomics: the same bits every run). */
+int efg_det_eval_max_pred(void);
+int efg_det_eval_max_gt(void);
+int efg_det_eval_pair_weights_f32(const float* pred_boxes, const int32_t* pred_labels, const int32_t* pred_off,
+                                  const float* gt_boxes, const int32_t* gt_labels, const int32_t* gt_off,
+                                  const int64_t* blk_off, int n_frames, int max_pred, int max_gt, float thr_vehicle,
+                                  float thr_pedestrian, float thr_cyclist, float* weights, void* stream);
+int efg_det_eval_assign_f32(const float* weights, const int64_t* blk_off, const int32_t* pred_off, const int32_t* gt_off,
+                            const int32_t* problems, int n_problems, int max_pred, int max_gt, const float* scores,
+                            const float* pred_boxes, const float* gt_boxes, const int32_t* gt_level, int32_t* counts,
+                            double* sums, void* stream);
+int efg_det_eval_accumulate(const int32_t* counts, const double* sums, const int32_t* problems, int n_problems,
+                            int64_t* total_counts, double* total_sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
