@@ -98,18 +98,15 @@ _SIGS = {
     "efg_points_transform_filter_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_size_t, c_void_p]),
     "efg_points_gather_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
-    "efg_match_cost_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_float] * 6 + [c_void_p, c_void_p]),
+    "efg_match_cost_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_float] * 6 + [c_void_p] * 3),
     "efg_focal_loss_forward_f32": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_float, c_void_p, c_void_p,
                                            c_void_p]),
     "efg_focal_loss_backward_f32": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_float, c_void_p,
                                             c_void_p, c_void_p, c_void_p]),
-    "efg_box_loss_forward_f32": (c_int, [c_void_p] * 6 + [c_int64] + [c_int] * 4 + [c_void_p] * 3),
-    "efg_box_loss_backward_f32": (c_int, [c_void_p] * 6 + [c_int64] + [c_int] * 4 + [c_void_p] * 4),
+    "efg_box_loss_forward_f32": (c_int, [c_void_p] * 6 + [c_int64] + [c_int] * 4 + [c_void_p] * 4),
+    "efg_box_loss_backward_f32": (c_int, [c_void_p] * 6 + [c_int64] + [c_int] * 4 + [c_void_p] * 5),
     "efg_rot_giou_paired_forward_f32": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 4),
     "efg_rot_giou_paired_backward_f32": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 5),
-    "efg_match_cost_rot_f32": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_float] * 6 + [c_void_p] * 3),
-    "efg_box_loss_rot_forward_f32": (c_int, [c_void_p] * 6 + [c_int64] + [c_int] * 4 + [c_void_p] * 4),
-    "efg_box_loss_rot_backward_f32": (c_int, [c_void_p] * 6 + [c_int64] + [c_int] * 4 + [c_void_p] * 5),
     "efg_bn_workspace_bytes": (c_size_t, [c_int]),
     "efg_bn_forward_f32": (c_int, [c_void_p] * 7 + [c_float, c_float, c_int64, c_int, c_int] + [c_void_p] * 4 +
                            [c_size_t, c_void_p]),

@@ -9,44 +9,26 @@
 //   focal_grad_kernel      its gradient w.r.t. the logits
 //   box_loss_kernel        per-layer sums of L1(xyz,lwh), 1 - GIoU3D, |d rad| over matched (prediction, target) pairs
 //   box_loss_grad_kernel   gradient w.r.t. the predicted boxes (a query is matched at most once: plain stores)
-// Reductions are one workgroup per layer with a fixed tree: deterministic.
+// Reductions are one workgroup per layer with a fixed tree: deterministic.  The GIoU3D term of the cost and of the box loss is
+// axis-aligned or heading-aware (giou3d.h): each of the three kernels that hold it is one template over that choice.
 #include "common.h"
+#include "giou3d.h"
 
 #include <algorithm>
 
 namespace efg {
 namespace {
 
-__device__ __forceinline__ float nan_to_num(float v) {  // torch.nan_to_num defaults
-  if (v != v) return 0.0f;
-  if (v == INFINITY) return 3.4028234663852886e38f;
-  if (v == -INFINITY) return -3.4028234663852886e38f;
-  return v;
-}
-
-// axis-aligned 3-D GIoU of (centre, size) boxes, as utils.paired_box3d_giou on box_cxcyczlwh_to_xyxyxy
-__device__ __forceinline__ float giou3d(const float* s, const float* t) {
-  float inter = 1.f, vol = 1.f, v1 = 1.f, v2 = 1.f;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float slo = nan_to_num(s[k] - 0.5f * s[3 + k]), shi = nan_to_num(s[k] + 0.5f * s[3 + k]);
-    const float tlo = nan_to_num(t[k] - 0.5f * t[3 + k]), thi = nan_to_num(t[k] + 0.5f * t[3 + k]);
-    v1 *= shi - slo;
-    v2 *= thi - tlo;
-    inter *= fmaxf(fminf(shi, thi) - fmaxf(slo, tlo), 0.f);
-    vol *= fmaxf(fmaxf(shi, thi) - fminf(slo, tlo), 0.f);
-  }
-  const float uni = v1 + v2 - inter;
-  return inter / uni - (vol - uni) / vol;
-}
-
 struct CostW {
   float w_class, w_bbox, w_giou, w_rad, alpha, gamma;
 };
 
+// GIoU (here and in the box-loss kernels): AlignedGIoU | RotatedGIoU of giou3d.h
+template <class GIoU>
 __global__ void __launch_bounds__(256)
 match_cost_kernel(const float* __restrict__ logits, const float* __restrict__ boxes, const long long* __restrict__ tgt_labels,
-                  const float* __restrict__ tgt_boxes, int P, int B, int Q, int C, int G, CostW w, float* __restrict__ cost) {
+                  const float* __restrict__ tgt_boxes, int P, int B, int Q, int C, int G, CostW w, GIoU giou,
+                  float* __restrict__ cost) {
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
   if (e >= (long long)P * Q * G) return;
   const int g = (int)(e % G);
@@ -63,7 +45,8 @@ match_cost_kernel(const float* __restrict__ logits, const float* __restrict__ bo
 #pragma unroll
   for (int k = 0; k < 6; ++k) l1 += fabsf(bx[k] - tb[k]);
   const float rad = fabsf(bx[6] - tb[6]);
-  cost[e] = w.w_bbox * l1 + w.w_class * (pos - neg) + w.w_giou * (-giou3d(bx, tb)) + w.w_rad * rad;
+  const float gv = giou.value(bx, tb);
+  cost[e] = w.w_bbox * l1 + w.w_class * (pos - neg) + w.w_giou * (-gv) + w.w_rad * rad;
 }
 
 // ---- focal loss ------------------------------------------------------------------------------------
@@ -204,10 +187,11 @@ focal_grad_kernel(const float* __restrict__ logits, const int* __restrict__ tcls
 // ---- box losses over matched pairs ---------------------------------------------------------------------
 // boxes [L][B][Q][7]; pair i: prediction (l_i, b_i, q_i), target tgt[b_i][g_i]; out[l][0..2] = (sum L1 of the 6
 // box numbers, sum (1 - GIoU), sum |d rad|) / denom
+template <class GIoU>
 __global__ void __launch_bounds__(1024)
 box_loss_kernel(const float* __restrict__ boxes, const float* __restrict__ tgt, const long long* __restrict__ li,
                 const long long* __restrict__ bi, const long long* __restrict__ qi, const long long* __restrict__ gi,
-                long long n, int B, int Q, int G, const float* __restrict__ denom, float* __restrict__ out) {
+                long long n, int B, int Q, int G, const float* __restrict__ denom, GIoU giou, float* __restrict__ out) {
   __shared__ float sm[16];
   const int l = blockIdx.x;
   float a0 = 0.f, a1 = 0.f, a2 = 0.f;
@@ -219,7 +203,7 @@ box_loss_kernel(const float* __restrict__ boxes, const float* __restrict__ tgt, 
 #pragma unroll
     for (int k = 0; k < 6; ++k) l1 += fabsf(s[k] - t[k]);
     a0 += l1;
-    a1 += 1.f - giou3d(s, t);
+    a1 += 1.f - giou.value(s, t);
     a2 += fabsf(s[6] - t[6]);
   }
   const float s0 = block_sum_1024(a0, sm), s1 = block_sum_1024(a1, sm), s2 = block_sum_1024(a2, sm);
@@ -233,11 +217,12 @@ box_loss_kernel(const float* __restrict__ boxes, const float* __restrict__ tgt, 
 __device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
 // gout [L][3]; gboxes [L][B][Q][7] must be zero-filled (only matched rows are written; a row is matched once)
+template <class GIoU>
 __global__ void __launch_bounds__(256)
 box_loss_grad_kernel(const float* __restrict__ boxes, const float* __restrict__ tgt, const long long* __restrict__ li,
                      const long long* __restrict__ bi, const long long* __restrict__ qi, const long long* __restrict__ gi,
                      long long n, int B, int Q, int G, const float* __restrict__ denom, const float* __restrict__ gout,
-                     float* __restrict__ gboxes) {
+                     GIoU giou, float* __restrict__ gboxes) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n || qi[i] < 0 || qi[i] >= Q) return;  // unmatched column: nothing to write (never index out of range)
   const long long row = ((li[i] * B + bi[i]) * Q + qi[i]) * 7;
@@ -245,61 +230,16 @@ box_loss_grad_kernel(const float* __restrict__ boxes, const float* __restrict__ 
   const float* t = tgt + (bi[i] * G + gi[i]) * 7;
   const float inv = 1.0f / denom[0];
   const float g_l1 = gout[li[i] * 3 + 0] * inv, g_gi = gout[li[i] * 3 + 1] * inv, g_rd = gout[li[i] * 3 + 2] * inv;
+  // The GIoU share first, summed from -0 (x + -0 is x for every x, a zero of either sign included, so the share is exact and
+  // the L1 share is unchanged where there is none); the L1 signs are added at the store, so that they are not held in
+  // registers across the geometry.
   float g[7];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) g[k] = g_l1 * sgn(s[k] - t[k]);
-  g[6] = g_rd * sgn(s[6] - t[6]);
-  // loss_giou = 1 - giou = 2 - inter/union - union/vol
-  // The intersection and enclosing sides are clamp(raw, min = 0), and autograd's clamp passes the gradient for raw >= 0 -- also
-  // at raw == 0 exactly, two boxes that touch on a face (the clamped value alone cannot tell that from separated boxes): the
-  // unclamped differences are kept and tested with >=, as the PyTorch composite (detection3d/losses.py) differentiates.
-  float slo[3], shi[3], tlo[3], thi[3], ik[3], ek[3], iraw[3], eraw[3];
-  float inter = 1.f, vol = 1.f, v1 = 1.f, v2 = 1.f;
+  for (int k = 0; k < 7; ++k) g[k] = -0.0f;
+  giou.add_loss_grad(s, t, g_gi, g);
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    slo[k] = s[k] - 0.5f * s[3 + k];
-    shi[k] = s[k] + 0.5f * s[3 + k];
-    tlo[k] = t[k] - 0.5f * t[3 + k];
-    thi[k] = t[k] + 0.5f * t[3 + k];
-    v1 *= shi[k] - slo[k];
-    v2 *= thi[k] - tlo[k];
-    iraw[k] = fminf(shi[k], thi[k]) - fmaxf(slo[k], tlo[k]);
-    eraw[k] = fmaxf(shi[k], thi[k]) - fminf(slo[k], tlo[k]);
-    ik[k] = fmaxf(iraw[k], 0.f);
-    ek[k] = fmaxf(eraw[k], 0.f);
-    inter *= ik[k];
-    vol *= ek[k];
-  }
-  const float uni = v1 + v2 - inter;
-  // d loss / d inter, d union, d vol
-  const float d_inter_direct = -1.f / uni, d_uni = inter / (uni * uni) - 1.f / vol, d_vol = uni / (vol * vol);
-  const float d_inter = d_inter_direct - d_uni;  // union = v1 + v2 - inter
-  const float d_v1 = d_uni;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
-    float g_hi = 0.f, g_lo = 0.f;
-    // vol1 = prod (shi - slo)
-    const float dv1 = d_v1 * (shi[k1] - slo[k1]) * (shi[k2] - slo[k2]);
-    g_hi += dv1;
-    g_lo -= dv1;
-    // inter_k = clamp(min(shi, thi) - max(slo, tlo), 0)
-    if (iraw[k] >= 0.f) {
-      const float di = d_inter * ik[k1] * ik[k2];
-      if (shi[k] < thi[k]) g_hi += di; else if (shi[k] == thi[k]) g_hi += 0.5f * di;
-      if (slo[k] > tlo[k]) g_lo -= di; else if (slo[k] == tlo[k]) g_lo -= 0.5f * di;
-    }
-    // enc_k = clamp(max(shi, thi) - min(slo, tlo), 0)
-    if (eraw[k] >= 0.f) {
-      const float de = d_vol * ek[k1] * ek[k2];
-      if (shi[k] > thi[k]) g_hi += de; else if (shi[k] == thi[k]) g_hi += 0.5f * de;
-      if (slo[k] < tlo[k]) g_lo -= de; else if (slo[k] == tlo[k]) g_lo -= 0.5f * de;
-    }
-    g[k] += g_gi * (g_hi + g_lo);
-    g[3 + k] += g_gi * 0.5f * (g_hi - g_lo);
-  }
-#pragma unroll
-  for (int k = 0; k < 7; ++k) gboxes[row + k] = g[k];
+  for (int k = 0; k < 6; ++k) gboxes[row + k] = g_l1 * sgn(s[k] - t[k]) + g[k];
+  gboxes[row + 6] = g_rd * sgn(s[6] - t[6]) + g[6];
 }
 
 
@@ -341,16 +281,21 @@ __global__ void __launch_bounds__(256) box_refine_bwd_kernel(const float* __rest
 
 using namespace efg;
 
+// frame: NULL = the axis-aligned GIoU, else the host float[4] of the rotated one (efg_hip.h)
 extern "C" int efg_match_cost_f32(const float* logits, const float* boxes, const int64_t* tgt_labels,
                                   const float* tgt_boxes, int p, int b, int q, int c, int g, float w_class, float w_bbox,
-                                  float w_giou, float w_rad, float alpha, float gamma, float* cost, void* stream) {
+                                  float w_giou, float w_rad, float alpha, float gamma, const float* frame, float* cost,
+                                  void* stream) {
   EFG_CHECK_ARG(p >= 0 && b >= 1 && q >= 0 && c >= 1 && g >= 0 && p % b == 0, "match_cost: bad sizes");
   const long long total = (long long)p * q * g;
   if (total == 0) return EFG_OK;
   EFG_CHECK_ARG(logits && boxes && tgt_labels && tgt_boxes && cost, "match_cost: null pointer");
-  hipLaunchKernelGGL(match_cost_kernel, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, logits,
-                     boxes, (const long long*)tgt_labels, tgt_boxes, p, b, q, c, g,
-                     CostW{w_class, w_bbox, w_giou, w_rad, alpha, gamma}, cost);
+  auto launch = [&](auto giou) {
+    hipLaunchKernelGGL(match_cost_kernel<decltype(giou)>, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0,
+                       (hipStream_t)stream, logits, boxes, (const long long*)tgt_labels, tgt_boxes, p, b, q, c, g,
+                       CostW{w_class, w_bbox, w_giou, w_rad, alpha, gamma}, giou, cost);
+  };
+  if (frame) launch(RotatedGIoU{load_frame(frame)}); else launch(AlignedGIoU{});
   EFG_LAUNCH_CHECK();
   return EFG_OK;
 }
@@ -390,13 +335,17 @@ extern "C" int efg_focal_loss_backward_f32(const float* logits, const int32_t* t
 
 extern "C" int efg_box_loss_forward_f32(const float* boxes, const float* tgt_boxes, const int64_t* l_idx,
                                         const int64_t* b_idx, const int64_t* q_idx, const int64_t* g_idx, int64_t n,
-                                        int layers, int b, int q, int g, const float* denom, float* out, void* stream) {
+                                        int layers, int b, int q, int g, const float* denom, const float* frame, float* out,
+                                        void* stream) {
   EFG_CHECK_ARG(layers >= 0 && n >= 0, "box_loss: bad sizes");
   if (layers == 0) return EFG_OK;
   EFG_CHECK_ARG(denom && out && (n == 0 || (boxes && tgt_boxes && l_idx && b_idx && q_idx && g_idx)), "box_loss: null pointer");
-  hipLaunchKernelGGL(box_loss_kernel, dim3(layers), dim3(1024), 0, (hipStream_t)stream, boxes, tgt_boxes,
-                     (const long long*)l_idx, (const long long*)b_idx, (const long long*)q_idx, (const long long*)g_idx,
-                     (long long)n, b, q, g, denom, out);
+  auto launch = [&](auto giou) {
+    hipLaunchKernelGGL(box_loss_kernel<decltype(giou)>, dim3(layers), dim3(1024), 0, (hipStream_t)stream, boxes, tgt_boxes,
+                       (const long long*)l_idx, (const long long*)b_idx, (const long long*)q_idx, (const long long*)g_idx,
+                       (long long)n, b, q, g, denom, giou, out);
+  };
+  if (frame) launch(RotatedGIoU{load_frame(frame)}); else launch(AlignedGIoU{});
   EFG_LAUNCH_CHECK();
   return EFG_OK;
 }
@@ -404,14 +353,18 @@ extern "C" int efg_box_loss_forward_f32(const float* boxes, const float* tgt_box
 extern "C" int efg_box_loss_backward_f32(const float* boxes, const float* tgt_boxes, const int64_t* l_idx,
                                          const int64_t* b_idx, const int64_t* q_idx, const int64_t* g_idx, int64_t n,
                                          int layers, int b, int q, int g, const float* denom, const float* grad_out,
-                                         float* grad_boxes, void* stream) {
+                                         const float* frame, float* grad_boxes, void* stream) {
   EFG_CHECK_ARG(layers >= 0 && n >= 0, "box_loss: bad sizes");
   if (n == 0) return EFG_OK;
   EFG_CHECK_ARG(boxes && tgt_boxes && l_idx && b_idx && q_idx && g_idx && denom && grad_out && grad_boxes,
                 "box_loss: null pointer");
-  hipLaunchKernelGGL(box_loss_grad_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, boxes,
-                     tgt_boxes, (const long long*)l_idx, (const long long*)b_idx, (const long long*)q_idx,
-                     (const long long*)g_idx, (long long)n, b, q, g, denom, grad_out, grad_boxes);
+  auto launch = [&](auto giou) {
+    hipLaunchKernelGGL(box_loss_grad_kernel<decltype(giou)>, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0,
+                       (hipStream_t)stream, boxes, tgt_boxes, (const long long*)l_idx, (const long long*)b_idx,
+                       (const long long*)q_idx, (const long long*)g_idx, (long long)n, b, q, g, denom, grad_out, giou,
+                       grad_boxes);
+  };
+  if (frame) launch(RotatedGIoU{load_frame(frame)}); else launch(AlignedGIoU{});
   EFG_LAUNCH_CHECK();
   return EFG_OK;
 }

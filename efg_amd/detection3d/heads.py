@@ -32,7 +32,7 @@ class Det3DHead(nn.Module):
         self.class_embed = get_clones(class_embed, num_layers)
         self.bbox_embed = get_clones(bbox_embed, num_layers)
         mc = config.model.loss.matcher
-        # model.loss.giou_type: "aligned" (the reference's axis-aligned GIoU) | "rotated" (heading-aware, csrc/rot_giou.hip),
+        # model.loss.giou_type: "aligned" (the reference's axis-aligned GIoU) | "rotated" (heading-aware, csrc/giou3d.h),
         # for the matching cost and loss_giou alike; the rotated one reads the box codes through the box coder's frame
         giou_type = config.model.loss.get("giou_type", "aligned")
         if giou_type not in GIOU_TYPES:

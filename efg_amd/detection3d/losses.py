@@ -14,7 +14,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from ..operators.det_loss import BoxLossLayers, BoxLossRotLayers, FocalLossLayers, check_giou_type, device_scalar
+from ..operators.det_loss import BoxLossLayers, FocalLossLayers, check_giou_type, device_scalar
 from .utils import box_cxcyczlwh_to_xyxyxy, paired_box3d_giou, paired_rot_giou3d, sigmoid_focal_loss
 
 
@@ -167,10 +167,8 @@ class Det3DLoss(nn.Module):
                 tcls.index_put_((l_idx, b_idx, q_idx), cls.to(torch.int32))
                 out["loss_ce"] = FocalLossLayers.apply(logits, tcls, denom, self.focal_alpha, 2.0)
             if want_box:
-                if self.giou_type == "rotated":
-                    sums = BoxLossRotLayers.apply(boxes, tgt_boxes, l_idx, b_idx, q_idx, g_idx, denom, self.frame)
-                else:
-                    sums = BoxLossLayers.apply(boxes, tgt_boxes, l_idx, b_idx, q_idx, g_idx, denom)   # [L, 3]
+                sums = BoxLossLayers.apply(boxes, tgt_boxes, l_idx, b_idx, q_idx, g_idx, denom,
+                                           self.frame if self.giou_type == "rotated" else None)   # [L, 3]
                 # the three families as ONE family-major [3 L] vector under a joint key: three column selects would put
                 # three SelectBackward nodes (zero-fill + copy + add each) into the graph, three times per step
                 out["loss_bbox|loss_giou|loss_rad"] = sums.t().reshape(-1)

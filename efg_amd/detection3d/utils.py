@@ -87,7 +87,7 @@ def paired_box3d_giou(boxes1, boxes2):
 
 
 # ---- heading-aware 3-D GIoU -------------------------------------------------------------------------------------------------
-# The plain PyTorch form of csrc/rot_giou.hip (same definition, same pair-local frame): the model's CPU path, the
+# The plain PyTorch form of rot_giou3d in csrc/giou3d.h (same definition, same pair-local frame): the model's CPU path, the
 # EFG_FUSED_LOSS=0 path on the GPU and, in float64, the yardstick of the kernels' tests.  Differentiable by autograd.
 def _inside_part(px, py, hx, hy, strict, ox, oy):
     """Green's-theorem share 1/2 sum cross(p0, p1) of the parts of a quadrilateral's four edges that lie inside the centred

@@ -30,7 +30,7 @@ def device_scalar(value, device):
 def match_cost(logits, boxes, tgt_labels, tgt_boxes, w_class, w_bbox, w_giou, w_rad, alpha=0.25, gamma=2.0, out=None,
                giou_type="aligned", frame=None):
     """logits [L,B,Q,C], boxes [L,B,Q,7], tgt_labels [B,G] int64, tgt_boxes [B,G,7] -> cost [L*B, Q, G] (into `out`, a
-    contiguous [L*B, Q, G] fp32 view, if given).  giou_type "rotated": the heading-aware GIoU (csrc/rot_giou.hip) of the boxes
+    contiguous [L*B, Q, G] fp32 view, if given).  giou_type "rotated": the heading-aware GIoU (csrc/giou3d.h) of the boxes
     read through `frame` = (sx, sy, yaw_scale, yaw_offset) in place of the axis-aligned one."""
     check_giou_type(giou_type, frame)
     L.require_gpu(logits, boxes, tgt_labels, tgt_boxes)
@@ -39,16 +39,10 @@ def match_cost(logits, boxes, tgt_labels, tgt_boxes, w_class, w_bbox, w_giou, w_
     lg, bx = logits.detach().contiguous().float(), boxes.detach().contiguous().float()
     cost = out if out is not None else torch.empty((n_layers * b, q, g), dtype=torch.float32, device=logits.device)
     assert cost.shape == (n_layers * b, q, g) and cost.dtype == torch.float32 and cost.is_contiguous()
-    if giou_type == "rotated":
-        L.check(L.lib().efg_match_cost_rot_f32(L.ptr(lg), L.ptr(bx), L.ptr(tgt_labels.contiguous()),
-                                               L.ptr(tgt_boxes.contiguous().float()), n_layers * b, b, q, c, g, float(w_class),
-                                               float(w_bbox), float(w_giou), float(w_rad), float(alpha), float(gamma),
-                                               frame_arg(frame), L.ptr(cost), L.stream()))
-        return cost
     L.check(L.lib().efg_match_cost_f32(L.ptr(lg), L.ptr(bx), L.ptr(tgt_labels.contiguous()),
                                        L.ptr(tgt_boxes.contiguous().float()), n_layers * b, b, q, c, g, float(w_class),
                                        float(w_bbox), float(w_giou), float(w_rad), float(alpha), float(gamma),
-                                       L.ptr(cost), L.stream()))
+                                       frame_arg(frame) if giou_type == "rotated" else None, L.ptr(cost), L.stream()))
     return cost
 
 
@@ -80,10 +74,10 @@ class FocalLossLayers(Function):
 
 class BoxLossLayers(Function):
     """boxes [L,B,Q,7], tgt_boxes [B,G,7], pair indices (l, b, q, g) int64 [n] -> [L, 3] (bbox L1, 1 - GIoU, rad L1)
-    sums / denom."""
+    sums / denom.  frame None: the axis-aligned GIoU; (sx, sy, yaw_scale, yaw_offset): the heading-aware one in column 1."""
 
     @staticmethod
-    def forward(ctx, boxes, tgt_boxes, l_idx, b_idx, q_idx, g_idx, denom):
+    def forward(ctx, boxes, tgt_boxes, l_idx, b_idx, q_idx, g_idx, denom, frame=None):
         n_layers, b, q = boxes.shape[:3]
         g = tgt_boxes.shape[1]
         bx, tb = boxes.contiguous(), tgt_boxes.contiguous()
@@ -91,8 +85,10 @@ class BoxLossLayers(Function):
         n = idx[0].numel()
         out = torch.empty((n_layers, 3), dtype=torch.float32, device=boxes.device)
         L.check(L.lib().efg_box_loss_forward_f32(L.ptr(bx), L.ptr(tb), *[L.ptr(t) for t in idx], n, n_layers, b, q, g,
-                                                 L.ptr(denom), L.ptr(out), L.stream()))
+                                                 L.ptr(denom), frame_arg(frame) if frame is not None else None,
+                                                 L.ptr(out), L.stream()))
         ctx.save_for_backward(bx, tb, *idx, denom)
+        ctx.frame = frame
         return out
 
     @staticmethod
@@ -103,38 +99,9 @@ class BoxLossLayers(Function):
         grad = torch.zeros_like(bx)
         L.check(L.lib().efg_box_loss_backward_f32(L.ptr(bx), L.ptr(tb), L.ptr(l_idx), L.ptr(b_idx), L.ptr(q_idx),
                                                   L.ptr(g_idx), l_idx.numel(), n_layers, b, q, tb.shape[1], L.ptr(denom),
-                                                  L.ptr(grad_out.contiguous()), L.ptr(grad), L.stream()))
-        return grad, None, None, None, None, None, None
-
-
-class BoxLossRotLayers(Function):
-    """BoxLossLayers with the heading-aware GIoU in column 1: boxes [L,B,Q,7], tgt_boxes [B,G,7], pair indices, denom, frame
-    (sx, sy, yaw_scale, yaw_offset) -> [L, 3] (bbox L1, 1 - rotated GIoU, rad L1) sums / denom."""
-
-    @staticmethod
-    def forward(ctx, boxes, tgt_boxes, l_idx, b_idx, q_idx, g_idx, denom, frame):
-        n_layers, b, q = boxes.shape[:3]
-        g = tgt_boxes.shape[1]
-        bx, tb = boxes.contiguous(), tgt_boxes.contiguous()
-        idx = [t.contiguous() for t in (l_idx, b_idx, q_idx, g_idx)]
-        n = idx[0].numel()
-        out = torch.empty((n_layers, 3), dtype=torch.float32, device=boxes.device)
-        L.check(L.lib().efg_box_loss_rot_forward_f32(L.ptr(bx), L.ptr(tb), *[L.ptr(t) for t in idx], n, n_layers, b, q, g,
-                                                     L.ptr(denom), frame_arg(frame), L.ptr(out), L.stream()))
-        ctx.save_for_backward(bx, tb, *idx, denom)
-        ctx.frame = tuple(float(v) for v in frame)
-        return out
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_out):
-        bx, tb, l_idx, b_idx, q_idx, g_idx, denom = ctx.saved_tensors
-        n_layers, b, q = bx.shape[:3]
-        grad = torch.zeros_like(bx)
-        L.check(L.lib().efg_box_loss_rot_backward_f32(L.ptr(bx), L.ptr(tb), L.ptr(l_idx), L.ptr(b_idx), L.ptr(q_idx),
-                                                      L.ptr(g_idx), l_idx.numel(), n_layers, b, q, tb.shape[1], L.ptr(denom),
-                                                      L.ptr(grad_out.contiguous()), frame_arg(ctx.frame), L.ptr(grad),
-                                                      L.stream()))
+                                                  L.ptr(grad_out.contiguous()),
+                                                  frame_arg(ctx.frame) if ctx.frame is not None else None, L.ptr(grad),
+                                                  L.stream()))
         return grad, None, None, None, None, None, None, None
 
 

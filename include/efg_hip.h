@@ -506,12 +506,15 @@ int efg_points_gather_f32(const float* points, const int64_t* index, int64_t m, 
  * Fused detection losses ($CQ/modules/matcher.py:40-80, $CQ/losses.py:26-108), all layers and scenes per launch.
  *   logits f32 [layers, b, q, c]; boxes f32 [layers, b, q, 7] (cx cy cz l w h rad, normalised);
  *   tgt_labels i64 [b, g], tgt_boxes f32 [b, g, 7] (zero padded); denom: device float (num_boxes).
+ *   frame (match cost and box loss): NULL = the reference's axis-aligned GIoU3D (heading ignored); else a HOST array of four
+ *   floats (sx, sy, yaw_scale, yaw_offset) = the heading-aware GIoU3D of the boxes read through it (see efg_rot_giou_paired_*).
+ *   Every other term and the per-layer reduction are the same for both.
  * ---------------------------------------------------------------------------------------- */
 /* cost f32 [p = layers*b, q, g] = w_bbox*L1(6) + w_class*(focal pos - neg cost at the GT label) + w_giou*(-GIoU3D)
  * + w_rad*|d rad|  (no gradient; feeds efg_lsap_f32) */
 int efg_match_cost_f32(const float* logits, const float* boxes, const int64_t* tgt_labels, const float* tgt_boxes,
                        int p, int b, int q, int c, int g, float w_class, float w_bbox, float w_giou, float w_rad,
-                       float alpha, float gamma, float* cost, void* stream);
+                       float alpha, float gamma, const float* frame, float* cost, void* stream);
 /* out[l] = sum over the n = b*q rows and c classes of sigmoid_focal_loss(logit, class == target_class[l, row]) / denom;
  * target_class i32 [layers, n], -1 = background row */
 int efg_focal_loss_forward_f32(const float* logits, const int32_t* target_class, int layers, int64_t n, int c,
@@ -524,12 +527,13 @@ int efg_focal_loss_backward_f32(const float* logits, const int32_t* target_class
  * backward: grad_boxes [layers, b, q, 7] must be zero-filled; a prediction is matched at most once. */
 int efg_box_loss_forward_f32(const float* boxes, const float* tgt_boxes, const int64_t* l_idx, const int64_t* b_idx,
                              const int64_t* q_idx, const int64_t* g_idx, int64_t n, int layers, int b, int q, int g,
-                             const float* denom, float* out, void* stream);
+                             const float* denom, const float* frame, float* out, void* stream);
 int efg_box_loss_backward_f32(const float* boxes, const float* tgt_boxes, const int64_t* l_idx, const int64_t* b_idx,
                               const int64_t* q_idx, const int64_t* g_idx, int64_t n, int layers, int b, int q, int g,
-                              const float* denom, const float* grad_out, float* grad_boxes, void* stream);
+                              const float* denom, const float* grad_out, const float* frame, float* grad_boxes,
+                              void* stream);
 
-/* Heading-aware 3-D GIoU of (cx, cy, cz, l, w, h, rad) boxes (csrc/rot_giou.hip): rotated-rectangle intersection and convex
+/* Heading-aware 3-D GIoU of (cx, cy, cz, l, w, h, rad) boxes (csrc/giou3d.h): rotated-rectangle intersection and convex
  * hull in the bird's-eye view times the z overlap / z range.  `frame` is a HOST array of four floats (sx, sy, yaw_scale,
  * yaw_offset): metric centre (cx sx, cy sy), size (l sx, w sy), yaw = rad yaw_scale + yaw_offset -- (pc_size_x, pc_size_y,
  * 2 pi, -pi) for the ConQueR codes, (1, 1, 1, 0) for metric boxes.
@@ -539,18 +543,6 @@ int efg_rot_giou_paired_forward_f32(const float* a, const float* b, int64_t n, c
                                     void* stream);
 int efg_rot_giou_paired_backward_f32(const float* a, const float* b, int64_t n, const float* frame, const float* grad_giou,
                                      float* grad_a, float* grad_b, void* stream);
-/* efg_match_cost_f32 / efg_box_loss_*_f32 with the rotated GIoU in place of the axis-aligned one (every other term and the
- * per-layer reduction as there). */
-int efg_match_cost_rot_f32(const float* logits, const float* boxes, const int64_t* tgt_labels, const float* tgt_boxes,
-                           int p, int b, int q, int c, int g, float w_class, float w_bbox, float w_giou, float w_rad,
-                           float alpha, float gamma, const float* frame, float* cost, void* stream);
-int efg_box_loss_rot_forward_f32(const float* boxes, const float* tgt_boxes, const int64_t* l_idx, const int64_t* b_idx,
-                                 const int64_t* q_idx, const int64_t* g_idx, int64_t n, int layers, int b, int q, int g,
-                                 const float* denom, const float* frame, float* out, void* stream);
-int efg_box_loss_rot_backward_f32(const float* boxes, const float* tgt_boxes, const int64_t* l_idx, const int64_t* b_idx,
-                                  const int64_t* q_idx, const int64_t* g_idx, int64_t n, int layers, int b, int q, int g,
-                                  const float* denom, const float* grad_out, const float* frame, float* grad_boxes,
-                                  void* stream);
 
 /* Unsorted top-k per row of x [rows, n] (the proposal selection, $CQ/transformer.py:65: torch.topk(sorted=False)):
  * values [rows, k], indices int64 [rows, k], in ascending index order; of the elements equal to the k-th largest value

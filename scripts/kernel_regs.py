@@ -5,18 +5,22 @@ import re
 import subprocess
 import sys
 import os
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+tree = ROOT
+if "--rev" in sys.argv:     # the sources AND the headers of that revision
+    at = sys.argv.index("--rev")
+    rev = sys.argv[at + 1]
+    del sys.argv[at:at + 2]
+    tree = tempfile.mkdtemp(prefix="kregs_")
+    archive = subprocess.check_output(["git", "-C", ROOT, "archive", rev, "efg_amd/csrc", "include"])
+    subprocess.run(["tar", "-x", "-C", tree], input=archive, check=True)
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 src, filt = args[0], (args[1] if len(args) > 1 else "")
-path = os.path.join(ROOT, "efg_amd", "csrc", src)
-if "--rev" in sys.argv:
-    rev = sys.argv[sys.argv.index("--rev") + 1]
-    text = subprocess.check_output(["git", "-C", ROOT, "show", "%s:efg_amd/csrc/%s" % (rev, src)])
-    path = "/tmp/kregs_" + src
-    open(path, "wb").write(text)
+path = os.path.join(tree, "efg_amd", "csrc", src)
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
-       "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "efg_amd", "csrc"), "-x", "hip",
+       "-ffp-contract=off", "-I" + os.path.join(tree, "include"), "-I" + os.path.join(tree, "efg_amd", "csrc"), "-x", "hip",
        "-c", path, "-o", "/tmp/kregs.o", "-Rpass-analysis=kernel-resource-usage"] + os.environ.get("KREGS_FLAGS", "").split()
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = None

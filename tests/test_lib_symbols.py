@@ -54,3 +54,39 @@ def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(_lib, "_LIB_PATH", "/nonexistent/libefg_hip.so")
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         _lib.lib()
+
+
+def _c_kind(decl):
+    """'ptr' | 'int' | 'int64_t' | 'size_t' | 'float' of a C return type or parameter declaration."""
+    if "*" in decl:
+        return "ptr"
+    words = [w for w in decl.split() if w != "const"]
+    assert words and words[0] in ("int", "int64_t", "size_t", "float"), "unclassified C type: %r" % decl
+    return words[0]
+
+
+def _ctypes_kind(t):
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "ptr"
+    return {ctypes.c_int: "int", ctypes.c_int64: "int64_t", ctypes.c_size_t: "size_t", ctypes.c_float: "float"}[t]
+
+
+def test_header_prototypes_match_the_ctypes_signatures():
+    """Every prototype of include/efg_hip.h against _lib._SIGS, return type and argument by argument (pointer, int, int64_t,
+    size_t or float): the two are kept by hand, and a call through a wrong argtypes list passes garbage without an error.
+    Declarations only: no built library."""
+    from efg_amd import _lib
+
+    header = open(os.path.join(ROOT, "include", "efg_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    header = re.sub(r"//[^\n]*", " ", header)
+    protos = re.findall(r"([\w\s\*]+?)\b(efg_\w+)\s*\(([^)]*)\)\s*;", header)
+    assert len(protos) >= 100 and len({name for _, name, _ in protos}) == len(protos)
+    declared = {}
+    for ret, name, params in protos:
+        params = [p for p in (q.strip() for q in params.split(",")) if p and p != "void"]
+        declared[name] = (_c_kind(ret), [_c_kind(p) for p in params])
+    bound = {name: (_ctypes_kind(res), [_ctypes_kind(a) for a in args]) for name, (res, args) in _lib._SIGS.items()}
+    assert sorted(declared) == sorted(bound)
+    wrong = {name: (declared[name], bound[name]) for name in declared if declared[name] != bound[name]}
+    assert not wrong, wrong

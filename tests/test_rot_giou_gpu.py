@@ -221,7 +221,7 @@ def box_case(n, device):
 def test_box_loss_rotated(dev, n):
     from efg_amd.detection3d.box_coder import VoxelBoxCoder3D
     from efg_amd.detection3d.utils import rot_giou3d
-    from efg_amd.operators.det_loss import BoxLossLayers, BoxLossRotLayers, device_scalar
+    from efg_amd.operators.det_loss import BoxLossLayers, device_scalar
 
     boxes, tgt, idx, grad_out, denom = box_case(n, dev)
     li, bi, qi, gi = idx
@@ -239,8 +239,8 @@ def test_box_loss_rotated(dev, n):
         (out * grad_out).sum().backward()
         return out.detach(), bx.grad
 
-    out, grad = run(BoxLossRotLayers, frame)
-    out2, grad2 = run(BoxLossRotLayers, frame)
+    out, grad = run(BoxLossLayers, frame)
+    out2, grad2 = run(BoxLossLayers, frame)
     assert torch.equal(out, out2) and torch.equal(grad, grad2)                     # deterministic reduction
     plain, _ = run(BoxLossLayers)
     assert torch.equal(out[:, 0], plain[:, 0]) and torch.equal(out[:, 2], plain[:, 2])
