@@ -8,7 +8,7 @@
 // and rebuilds centre / size / rotation / softmax in registers.  Backward returns gradients w.r.t. the
 // value map, the raw box offsets and the raw logits (softmax and geometry backward fused in).
 // Same lane mapping as msda.hip (LP = D/4 lanes x float4 per pair).  Encoder self-attention (queries on the
-// value grid, L*P <= 32) has its own backward in GEMM form, box_bwd_tile_kernel below; larger point counts
+// value grid, L*P <= 32) has its own backward in GEMM form, box_bwd_tile_a_kernel + box_bwd_tile_b_kernel below; larger point counts
 // accumulate grad_value in an fp64 LDS window like msda_bwd_grid_kernel.
 #include "common.h"
 #include <algorithm>
@@ -454,73 +454,154 @@ box_bwd_kernel(const float* __restrict__ value, const long long* __restrict__ sh
   }  // tile loop
 }
 
-// ---- encoder backward in GEMM form ---------------------------------------------------------------
-// Encoder self-attention: the queries ARE the cells of the (single-level) value map, so an 8x8 query tile only
-// touches the 16x16 window of cells around it.  Per (tile, head, scene) the whole backward then factors into two
-// small dense products plus SCALAR scatter / gather work -- no per-channel atomics and no per-point channel
-// gathers (the previous kernel issued 3200 fp64 LDS atomics and 100 float4 gathers per (query, head)):
+// ---- encoder backward in GEMM form: two passes per tile ----------------------------------------------------------------------
+// Encoder self-attention: the queries ARE the cells of the (single-level) value map, so a 4 x 8 query tile of one head only
+// touches the 12 x 16 window of cells around it (the tile + R = 4 cells).  Per (tile, head, scene) the whole backward then
+// factors into two small dense products plus SCALAR scatter / gather work -- no per-channel atomics and no per-point channel
+// gathers:
 //
-//   G [64 q  x 256 cells] = GO [64 x 32] . V^T [32 x 256]        (MFMA)   "what each cell's value says to q"
+//   G [32 q  x 192 cells] = GO [32 x 32] . V^T [32 x 192]        (MFMA)   "what each cell's value says to q"
 //       grad_attn(q, p)   = sum_corners wc * G[q][cell]                    4 scalar LDS reads per point
 //       grad_loc (q, p)   = bilinear differences of the same 4 scalars
-//   W [256 cells x 64 q]  += attn * wc   at the 4 corner cells             plain LDS read-modify-write: column q
-//                                                                          is private to its 4 corner lanes
-//   GV[256 cells x 32]    = W [256 x 64] . GO [64 x 32]           (MFMA)   -> one global atomic per touched
-//                                                                          (cell, channel) of the window
+//   W [192 cells x 32 q]  += attn * wc   at the 4 corner cells             plain LDS read-modify-write
+//   GV[192 cells x 32]    = W [192 x 32] . GO [32 x 32]           (MFMA)   -> the window's rows of grad_value
 //
-// G and W share one LDS buffer (pass A reads G, pass B rebuilds the geometry and fills W).  Sampling points
-// that leave the window (boxes grown past R = 4 cells) take a per-channel global path, as before.
-// Tile geometry of box_bwd_tile_kernel: TQY x 8 queries of one head, the window of R cells around them.
-//   TQY = 8: 64 queries, 16 x 16 window, 512 threads, 132 KB of LDS -> ONE workgroup per CU, all of its waves in the same
-//            phase (the round-2 kernel);
-//   TQY = 4: 32 queries, 12 x 16 window, 256 threads,  68 KB of LDS -> TWO workgroups per CU, whose phases (MFMA / LDS
-//            scatter / global flush) overlap; 1.5x the halo cells per query.
-template <int TQY_>
+// The two products share nothing but their inputs, and one kernel that holds both needs 256 VGPRs (two waves per SIMD, which
+// issue a third of their life: latency-bound).  So there is one kernel per product, each at 128 VGPRs = FOUR waves per SIMD,
+// whose phases (global loads / MFMA / LDS scatter / flush) overlap across the workgroups of a CU:
+//   box_bwd_tile_a_kernel  G = GO . V^T, then the gradients of the offsets and the logits.  G is written over the value window
+//                          (every wave holds its G blocks in registers until all reads of V are done): 40 KB of LDS.  It writes
+//                          nothing that overlaps, so ONE launch strides over all tiles.  It also counts the far corners per
+//                          bin and takes the largest |grad_out| for the binned path of pass B.
+//   box_bwd_tile_b_kernel  softmax + geometry again (a few hundred VALU instructions per tile), the W scatter, GV = W . GO and
+//                          the window flush: 37 KB of LDS.  One launch per colour class (plain read-modify-write flush), or one
+//                          launch over all tiles with float atomics.
+//
+// Lane mapping of both: 8 lanes per query = 4 corners x 2 halves of the lattice.  The kernels are bound by their VALU
+// instruction count, so the quad of a half works on 4 points at a time: each lane does the geometry of ITS point of the group
+// (tile_point), then for each of the 4 points the quad takes cell / fractions / weight from the owner lane by DPP and every
+// lane handles its own corner -- the LDS access pattern (4 distinct cells per quad and step) that the mapping keeps
+// conflict-free.  In pass A the owner collects the 4 corner values of G and the gradient arithmetic runs once per point.
+//
+// W: column q belongs to the 8 lanes of the query.  At one step the 4 corner lanes of a half hit 4 distinct cells, so a plain
+// read-modify-write is safe; the two halves take turns (their points may share a cell), and the LDS pipe keeps consecutive
+// steps of a wave in order.  (LDS float atomics instead of the 32 dependent round trips: 490 -> 726 us per launch, ds_add_f32
+// is far slower than the read + write it replaces.)
+//
+// Far corners: sampling points that leave the window (boxes grown past R cells).  As the boxes grow with training these stop
+// being rare, and 32 float atomics per corner are a cliff (2 x 35 344 queries with boxes 3x their anchors: 0.67 -> 39.8 ms per
+// call).  With a workspace a far corner is ONE 8-byte entry (grad_out row, weight) in the bin of its (cell, head) row: pass A
+// counts them, the host code scans the counts, pass B pushes and box_bin_reduce_kernel sums each bin.  Both passes classify a
+// corner with the same expressions on the same make_box_v / box_point values, so every entry finds its slot.
 struct BT {
-  static constexpr int TQY = TQY_, TQX = 8, R = 4, WINY = TQY + 2 * R, WINX = TQX + 2 * R, NQ = TQY * TQX, NC = WINY * WINX, D = 32;
+  static constexpr int TQY = 4, TQX = 8, R = 4, WINY = TQY + 2 * R, WINX = TQX + 2 * R, NQ = TQY * TQX, NC = WINY * WINX, D = 32;
+  static constexpr int PMAX = 32;      // L * P of this path
+  static constexpr int EPT = PMAX / 2; // points per lane (one half of the lattice)
   static constexpr int VS = 36;        // row stride of V / GO tiles (floats, 16-byte aligned rows)
   static constexpr int GS = NC + 4;    // G[q][cell]
   static constexpr int WS = NQ + 4;    // W[cell][q]
   static constexpr int kThreads = NQ * 8;
-  static constexpr int kGW = (NQ * GS > NC * WS) ? NQ * GS : NC * WS;
   static constexpr int NW = kThreads / 64, MB = NQ / 16, NB = NC / 16;   // waves, 16-query blocks, 16-cell blocks
   static constexpr int WPM = NW / MB, NBW = NB / WPM, CBW = NB / NW;     // S1: waves per query block, cell blocks per wave; S5
   static_assert(MB * WPM == NW && WPM * NBW == NB && NW * CBW == NB && NBW % 2 == 0, "tile shape does not divide over the waves");
+  // colour classes of pass B: the windows of two tiles (ty, tx) with the same (ty % NCY, tx % NCX) never overlap
+  static constexpr int NCY = (WINY + TQY - 1) / TQY, NCX = (WINX + TQX - 1) / TQX;
+  static constexpr int kVG = (NC * VS > NQ * GS) ? NC * VS : NQ * GS;    // pass A: V, then G over it
+  static constexpr size_t lds_bytes_a = sizeof(float) * (kVG + NQ * VS + 2 * NQ * PMAX + 2 * PMAX);
+  static constexpr size_t lds_bytes_b = sizeof(float) * (NC * WS + NQ * VS + NQ * PMAX + 2 * PMAX);
 };
-namespace bt {
-constexpr int PMAX = 32;  // L * P of the fused encoder path
-constexpr int TQX = 8, R = 4;
-template <int TQY>
-constexpr size_t lds_bytes() {
-  using B = BT<TQY>;
-  return sizeof(float) * (B::NC * B::VS + B::NQ * B::VS + B::kGW + 2 * B::NQ * PMAX + 2 * PMAX);
-}
-}  // namespace bt
-
-template <int K>
-__device__ __forceinline__ float quad_bcast(float v) {
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), K | (K << 2) | (K << 4) | (K << 6), 0xf, 0xf, true));
-}
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-template <int TQY>
-__global__ void __launch_bounds__(BT<TQY>::kThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
-box_bwd_tile_kernel(const float* __restrict__ value, const long long* __restrict__ shapes,
-                    const float* __restrict__ ref, const float* __restrict__ off, const float* __restrict__ logits,
-                    const float* __restrict__ kidx, const float* __restrict__ grad_out, BoxDims dm,
-                    float* __restrict__ grad_value, float* __restrict__ grad_off, float* __restrict__ grad_logits,
-                    int* __restrict__ cursor, int2* __restrict__ entries, const int* __restrict__ bin_end,
-                    int* __restrict__ overflow, int color) {
-  using B = BT<TQY>;
-  constexpr int TQX = B::TQX, R = B::R, WINY = B::WINY, WINX = B::WINX, NQ = B::NQ, NC = B::NC, D = B::D, VS = B::VS, GS = B::GS,
-                WS = B::WS, kThreads = B::kThreads, kGW = B::kGW, PMAX = bt::PMAX;
+// What the 8 lanes of a query read of its row, from the query clamped to the map (a tile may hang over the map's edge; such a
+// query computes on its neighbour's row and writes nothing).
+struct QueryRow {
+  long long bq;              // scene * Lq + the (clamped) query
+  float4 go;                 // this lane's 4 channels of the grad_out row
+  float lgv[4], rf[5], of[5];   // logits sub, sub + 8, ..; ref (x, y, l, w, angle); offsets
+};
+// ... and puts the grad_out row into the GO tile (`go_dst`: this lane's 4 floats; zeros for a query past the edge)
+__device__ __forceinline__ QueryRow load_query_row(const float* __restrict__ ref, const float* __restrict__ off,
+                                                   const float* __restrict__ logits, const float* __restrict__ grad_out,
+                                                   const BoxDims& dm, int Hm, int Wm, int bi, int m, int qy, int qx, bool qok,
+                                                   int sub, float* go_dst) {
+  QueryRow q;
+  const int np = dm.p, qyc = min(qy, Hm - 1), qxc = min(qx, Wm - 1);
+  q.bq = (long long)bi * dm.lq + (long long)qyc * Wm + qxc;
+  q.go = ld4(grad_out + (q.bq * dm.h + m) * BT::D + sub * 4);
+  *reinterpret_cast<float4*>(go_dst) = qok ? q.go : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) q.lgv[k] = logits[q.bq * dm.lg_rs + m * np + min(sub + 8 * k, np - 1)];
+  const float* r = ref + q.bq * 7;
+  q.rf[0] = r[0], q.rf[1] = r[1], q.rf[2] = r[3], q.rf[3] = r[4], q.rf[4] = r[6];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) q.of[k] = off[q.bq * dm.off_rs + m * dm.v + min(k, dm.v - 1)];
+  return q;
+}
+
+// softmax statistics of a query's np <= 32 logits over its 8 lanes (lane `sub` holds logits sub, sub + 8, ..): the
+// un-normalised weights into as[0 .. np), returns 1 / their sum
+__device__ __forceinline__ float softmax_stats8(const float lgv[4], int sub, int np, float* as) {
+  float mx = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (sub + 8 * k < np) mx = fmaxf(mx, lgv[k]);
+#pragma unroll
+  for (int dlt = 4; dlt > 0; dlt >>= 1) mx = fmaxf(mx, __shfl_xor(mx, dlt, 64));
+  float den = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (sub + 8 * k < np) {
+      const float ex = expf(lgv[k] - mx);
+      as[sub + 8 * k] = ex;
+      den += ex;
+    }
+#pragma unroll
+  for (int dlt = 4; dlt > 0; dlt >>= 1) den += __shfl_xor(den, dlt, 64);
+  return 1.0f / den;
+}
+
+// The point `op` of the lattice that a lane owns in one group of 4: where it lands on the map and what it weighs.
+struct TilePoint {
+  bool own;                  // a real point of a real query
+  float kxn, kyn, wgt;       // lattice offsets, attention weight (0 when not own)
+  BoxPx px;
+  int h_pub, w_low;          // top-left corner cell; h_pub = -(1 << 20) for a point that samples nothing: no corner of it is "ok"
+  float lh, lwf;             // bilinear fractions
+};
+__device__ __forceinline__ TilePoint tile_point(const BoxGeo& g, const float* k_s, const float* as, float inv, int op, bool qok,
+                                                int np, int Hm, int Wm) {
+  TilePoint t;
+  t.own = qok && op < np;
+  t.kxn = t.own ? k_s[op * 2] : 0.f;
+  t.kyn = t.own ? k_s[op * 2 + 1] : 0.f;
+  t.px = box_point(g, t.kxn, t.kyn, Hm, Wm);
+  t.wgt = t.own ? as[op] * inv : 0.f;
+  const float h_im = t.px.h_im, w_im = t.px.w_im;
+  const bool inside = t.own && (h_im > -1.f) && (w_im > -1.f) && (h_im < (float)Hm) && (w_im < (float)Wm);
+  const int h_low = (int)floorf(h_im);
+  t.w_low = (int)floorf(w_im);
+  t.lh = h_im - (float)h_low;
+  t.lwf = w_im - (float)t.w_low;
+  t.h_pub = inside ? h_low : -(1 << 20);
+  return t;
+}
+
+// ---- pass A: G = GO . V^T, grad_offsets, grad_logits ------------------------------------------------------------------------
+__global__ void __launch_bounds__(BT::kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+box_bwd_tile_a_kernel(const float* __restrict__ value, const long long* __restrict__ shapes, const float* __restrict__ ref,
+                      const float* __restrict__ off, const float* __restrict__ logits, const float* __restrict__ kidx,
+                      const float* __restrict__ grad_out, BoxDims dm, float* __restrict__ grad_off,
+                      float* __restrict__ grad_logits, int* __restrict__ counts, unsigned* __restrict__ absmax) {
+  // counts / absmax (both or neither): what box_bin_count_kernel and absmax_bits_kernel compute for the decoder's bins, here
+  // for the far corners -- this pass classifies every corner with the test pass B pushes with and reads every grad_out row once
+  constexpr int TQY = BT::TQY, TQX = BT::TQX, R = BT::R, WINY = BT::WINY, WINX = BT::WINX, NQ = BT::NQ, NC = BT::NC, D = BT::D,
+                VS = BT::VS, GS = BT::GS, kThreads = BT::kThreads, PMAX = BT::PMAX, EPT = BT::EPT;
+  unsigned go_max = 0u;
   extern __shared__ float lds[];
-  float* Vs = lds;                     // [NC][VS]
-  float* GOs = Vs + NC * VS;           // [NQ][VS]
-  float* GW = GOs + NQ * VS;           // G [NQ][GS]  |  W [NC][WS]
-  float* a_s = GW + kGW;               // [NQ][PMAX] un-normalised softmax weights
+  float* VG = lds;                     // V [NC][VS] in S0 / S1, then G [NQ][GS]
+  float* GOs = VG + BT::kVG;           // [NQ][VS]
+  float* a_s = GOs + NQ * VS;          // [NQ][PMAX] un-normalised softmax weights
   float* ga_s = a_s + NQ * PMAX;       // [NQ][PMAX]
   float* k_s = ga_s + NQ * PMAX;       // [PMAX][2] the k x k lattice (read at every point: keep it out of global)
   const int Hm = (int)shapes[0], Wm = (int)shapes[1];
@@ -530,376 +611,10 @@ box_bwd_tile_kernel(const float* __restrict__ value, const long long* __restrict
   const int slot = tid >> 3, sub = tid & 7, corner = sub & 3, half = sub >> 2;
   const int m = blockIdx.y, bi = blockIdx.z;
   const int np = dm.p;  // single level
-  const int tiles_x = (Wm + TQX - 1) / TQX;
-  const int tiles_y = (Hm + TQY - 1) / TQY;
-  // color >= 0: this launch works on the tiles (ty, tx) with (ty % NCY, tx % NCX) == (color / NCX, color % NCX) only.  The
-  // windows of two such tiles never overlap (a window is the tile + R cells all around: NCY x NCX tiles), so the window
-  // flush is a plain read-modify-write and the NCY * NCX launches apply the overlapping windows' contributions to a cell
-  // in a FIXED order: grad_value is reproducible bit for bit.  color < 0: one launch over all tiles, float atomics.
-  constexpr int NCY = (WINY + TQY - 1) / TQY, NCX = (WINX + TQX - 1) / TQX;
-  const int cy0 = color >= 0 ? color / NCX : 0, cx0 = color >= 0 ? color % NCX : 0;
-  const int sy = color >= 0 ? NCY : 1, sx = color >= 0 ? NCX : 1;
-  const int ctx = (tiles_x - cx0 + sx - 1) / sx, cty = (tiles_y - cy0 + sy - 1) / sy;   // tiles of this launch
-  const int ntiles = max(ctx, 0) * max(cty, 0);
-  auto tile_of = [&](int j) { return (cy0 + sy * (j / ctx)) * tiles_x + cx0 + sx * (j % ctx); };
-  const long long S = dm.s;
-  constexpr int VPT = NC * (D / 4) / kThreads;  // float4 of the value window per thread (4)
-  constexpr int EPT = PMAX / 2;                 // points per lane (one half of the lattice)
-
-  // Everything a work item reads from global memory, fetched one item ahead: with 132 KB of LDS there is one
-  // workgroup per CU and all of its waves sit in the same phase, so nothing else would hide the latency.
-  struct Pre {
-    float4 v[VPT];
-    float4 go;
-    float lg[4], rf[5], of[5];
-  } pre;
-  auto fetch = [&](int j) {
-    const int tile = tile_of(j);
-    const int ty0 = (tile / tiles_x) * TQY, tx0 = (tile % tiles_x) * TQX;
-#pragma unroll
-    for (int it = 0; it < VPT; ++it) {
-      const int idx = tid + it * kThreads;
-      const int cell = idx >> 3, c4 = (idx & 7) * 4;
-      const int cy = min(max(ty0 - R + cell / WINX, 0), Hm - 1), cx = min(max(tx0 - R + cell % WINX, 0), Wm - 1);
-      pre.v[it] = ld4(value + (((long long)bi * S + (long long)cy * Wm + cx) * dm.h + m) * D + c4);
-    }
-    const int qy = min(ty0 + slot / TQX, Hm - 1), qx = min(tx0 + slot % TQX, Wm - 1);
-    const long long bq = (long long)bi * dm.lq + (long long)qy * Wm + qx, t = bq * dm.h + m;
-    pre.go = ld4(grad_out + t * D + sub * 4);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) pre.lg[k] = logits[bq * dm.lg_rs + m * np + min(sub + 8 * k, np - 1)];
-    const float* r = ref + bq * 7;
-    pre.rf[0] = r[0];
-    pre.rf[1] = r[1];
-    pre.rf[2] = r[3];
-    pre.rf[3] = r[4];
-    pre.rf[4] = r[6];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) pre.of[k] = off[bq * dm.off_rs + m * dm.v + min(k, dm.v - 1)];
-  };
-  if ((int)blockIdx.x < ntiles) fetch(blockIdx.x);
-
-  for (int tj = blockIdx.x; tj < ntiles; tj += gridDim.x) {
-    const int tile = tile_of(tj);
-    const int ty0 = (tile / tiles_x) * TQY, tx0 = (tile % tiles_x) * TQX;
-    const int wy0 = ty0 - R, wx0 = tx0 - R;
-    __syncthreads();  // previous item's GEMM-2 is done with GOs / W
-    // ---- S0: registers -> LDS ------------------------------------------------------------------------------
-#pragma unroll
-    for (int it = 0; it < VPT; ++it) {
-      const int idx = tid + it * kThreads;
-      const int cell = idx >> 3, c4 = (idx & 7) * 4;
-      const int cy = wy0 + cell / WINX, cx = wx0 + cell % WINX;
-      const bool in = cy >= 0 && cy < Hm && cx >= 0 && cx < Wm;
-      *reinterpret_cast<float4*>(Vs + cell * VS + c4) = in ? pre.v[it] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    const int qy = ty0 + slot / TQX, qx = tx0 + slot % TQX;
-    const bool qok = qy < Hm && qx < Wm;
-    const long long bqs = qok ? ((long long)bi * dm.lq + (long long)qy * Wm + qx) : 0;
-    const long long t = bqs * dm.h + m;
-    *reinterpret_cast<float4*>(GOs + slot * VS + sub * 4) = qok ? pre.go : make_float4(0.f, 0.f, 0.f, 0.f);
-    // softmax statistics of the pair (8 lanes share the work)
-    float* as = a_s + slot * PMAX;
-    float mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (sub + 8 * k < np) mx = fmaxf(mx, pre.lg[k]);
-#pragma unroll
-    for (int dlt = 4; dlt > 0; dlt >>= 1) mx = fmaxf(mx, __shfl_xor(mx, dlt, 64));
-    float den = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (sub + 8 * k < np) {
-        const float ex = expf(pre.lg[k] - mx);
-        as[sub + 8 * k] = ex;
-        den += ex;
-      }
-#pragma unroll
-    for (int dlt = 4; dlt > 0; dlt >>= 1) den += __shfl_xor(den, dlt, 64);
-    const float inv = 1.0f / den;
-    const BoxGeo g = make_box_v(pre.rf, pre.of, dm.v);
-    __syncthreads();
-    if (tj + (int)gridDim.x < ntiles) fetch(tj + gridDim.x);  // in flight during the phases below
-
-    // ---- S1: G = GO . V^T ----------------------------------------------------------------------------------
-    {
-      const int mb = wave / B::WPM, nb0 = (wave % B::WPM) * B::NBW;
-      const int r16 = lane & 15, kk = lane >> 4;
-      float a[8];
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) a[ks] = GOs[(16 * mb + r16) * VS + 4 * ks + kk];
-#pragma unroll
-      for (int nbi = 0; nbi < B::NBW; nbi += 2) {
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        const float* b0 = Vs + (16 * (nb0 + nbi) + r16) * VS + kk;
-        const float* b1 = b0 + 16 * VS;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ks], b0[4 * ks], acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ks], b1[4 * ks], acc1, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float* gp = GW + (16 * mb + 4 * kk + r) * GS + 16 * (nb0 + nbi) + r16;
-          gp[0] = acc0[r];
-          gp[16] = acc1[r];
-        }
-      }
-    }
-    __syncthreads();
-
-    // ---- S2 (pass A): this lane = (query, corner, half of the lattice).  Gradients wrt the attention weights
-    // and the sampling locations come from 4 scalars of G per point; the (cell, weight) of the lane's corner is
-    // kept in registers for pass B.
-    // The kernel is bound by its VALU instruction count (static count of this pass in the first version: 2400 of the
-    // 5300 per tile and wave), and there all 4 corner lanes of a point redid the point's geometry and its gradient
-    // arithmetic.  Now the quad works on 4 points at a time: each lane does the geometry of ITS point of the group,
-    // then for each of the 4 points the quad takes cell / fractions / weight from the owner lane by DPP, every lane reads
-    // G at its corner (the LDS access pattern that the quad mapping keeps conflict-free) and the owner collects the 4
-    // corner values; the gradient arithmetic runs once per point, on the owner.
-    float dcx = 0.f, dcy = 0.f, dw = 0.f, dh = 0.f, dth = 0.f, dot = 0.f;
-    int e_cell[EPT];    // window cell (>= 0), -1: nothing to add, -2: outside the window (global path)
-    float e_w[EPT];
-    const int cyo = corner >> 1, cxo = corner & 1;
-    const float sy = cyo ? 1.f : -1.f, ay = cyo ? 0.f : 1.f, sx = cxo ? 1.f : -1.f, ax = cxo ? 0.f : 1.f;
-#pragma unroll
-    for (int j = 0; j < EPT / 4; ++j) {
-      const int op = half + 2 * (4 * j + corner);   // the point this lane owns in group j
-      const bool own = qok && op < np;
-      const float kxn = own ? k_s[op * 2] : 0.f, kyn = own ? k_s[op * 2 + 1] : 0.f;
-      const BoxPx px = box_point(g, kxn, kyn, Hm, Wm);
-      const float wgt = own ? as[op] * inv : 0.f;
-      const float h_im = px.h_im, w_im = px.w_im;
-      const bool inside = own && (h_im > -1.f) && (w_im > -1.f) && (h_im < (float)Hm) && (w_im < (float)Wm);
-      const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
-      const float lh = h_im - (float)h_low, lwf = w_im - (float)w_low;
-      const int h_pub = inside ? h_low : -(1 << 20);   // no corner of a point that samples nothing is "ok"
-      float gq[4] = {0.f, 0.f, 0.f, 0.f};              // G at the 4 corners of the OWN point
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int k = 4 * j + c;
-        const int hb = quad_bcast_i(h_pub, c), wb = quad_bcast_i(w_low, c);
-        const float lhb = quad_bcast_f(lh, c), lwb = quad_bcast_f(lwf, c), wgb = quad_bcast_f(wgt, c);
-        const int cy = hb + cyo, cx = wb + cxo;
-        const bool ok = (unsigned)cy < (unsigned)Hm && (unsigned)cx < (unsigned)Wm;
-        const int ly = cy - wy0, lx = cx - wx0;
-        const bool in_win = (unsigned)ly < (unsigned)WINY && (unsigned)lx < (unsigned)WINX;
-        e_cell[k] = -1;
-        e_w[k] = 0.f;
-        float gval = 0.f;
-        if (ok) {
-          // ((corner >> 1) ? lh : 1 - lh) * ((corner & 1) ? lw : 1 - lw): one rounding each, as the select form
-          e_w[k] = wgb * (fmaf(sy, lhb, ay) * fmaf(sx, lwb, ax));
-          if (in_win) {
-            e_cell[k] = ly * WINX + lx;
-            gval = GW[slot * GS + e_cell[k]];
-          } else {  // the box has grown out of the window: dot product against the global value row
-            e_cell[k] = -2;
-            // (rare on a fresh model, common once the boxes have grown: 16-byte loads, the same 32 additions in order)
-            const float4* vr = reinterpret_cast<const float4*>(value + (((long long)bi * S + (long long)cy * Wm + cx) * dm.h + m) * D);
-            const float4* gr = reinterpret_cast<const float4*>(GOs + slot * VS);
-#pragma unroll 1
-            for (int cc = 0; cc < D / 4; ++cc) {
-              const float4 v4 = vr[cc], g4 = gr[cc];
-              gval = fmaf(g4.w, v4.w, fmaf(g4.z, v4.z, fmaf(g4.y, v4.y, fmaf(g4.x, v4.x, gval))));
-            }
-          }
-        }
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) {
-          const float t4 = quad_bcast_f(gval, cc);
-          gq[cc] = (corner == c) ? t4 : gq[cc];
-        }
-      }
-      const float g0 = gq[0], g1 = gq[1], g2 = gq[2], g3 = gq[3];
-      const float hh = 1.f - lh, hw = 1.f - lwf;
-      const float gx = px.gx, gy = px.gy;
-      const float ga = fmaf(lh * lwf, g3, fmaf(lh * hw, g2, fmaf(hh * lwf, g1, hh * hw * g0)));
-      const float gwl = (float)Wm * wgt * fmaf(hh, g1 - g0, lh * (g3 - g2));
-      const float ghl = (float)Hm * wgt * fmaf(hw, g2 - g0, lwf * (g3 - g1));
-      dcx += gwl;
-      dcy += ghl;
-      dw += kxn * (gwl * g.cs + ghl * g.sn);
-      dh += kyn * (ghl * g.cs - gwl * g.sn);
-      dth += gwl * (-(gx * g.sn) - gy * g.cs) + ghl * (gx * g.cs - gy * g.sn);
-      dot = fmaf(wgt, ga, dot);
-      if (own) ga_s[slot * PMAX + op] = ga;
-    }
-    // every lane holds the sums over its own points: 4 corner lanes of a half, then the two halves 4 lanes apart
-    dcx = quad_sum(dcx);
-    dcy = quad_sum(dcy);
-    dw = quad_sum(dw);
-    dh = quad_sum(dh);
-    dth = quad_sum(dth);
-    dot = quad_sum(dot);
-    dcx += __shfl_xor(dcx, 4, 64);
-    dcy += __shfl_xor(dcy, 4, 64);
-    dw += __shfl_xor(dw, 4, 64);
-    dh += __shfl_xor(dh, 4, 64);
-    dth += __shfl_xor(dth, 4, 64);
-    dot += __shfl_xor(dot, 4, 64);
-    if (qok && sub == 0) {
-      float* go = grad_off + bqs * dm.off_rs + m * dm.v;
-      go[0] = dcx * g.rw / 8.0f;
-      go[1] = dcy * g.rh / 8.0f;
-      go[2] = g.w_on ? dw * g.rw / 8.0f : 0.0f;
-      go[3] = g.h_on ? dh * g.rh / 8.0f : 0.0f;
-      if (dm.v == 5) go[4] = dth * (2.0f * 3.14159274f / 16.0f);
-    }
-    __syncthreads();  // G fully consumed; ga_s complete
-    if (qok)
-      for (int e = sub; e < np; e += 8) grad_logits[bqs * dm.lg_rs + m * np + e] = as[e] * inv * (ga_s[slot * PMAX + e] - dot);
-
-    // ---- S3 / S4 (pass B): W[cell][q] = sum of attn * bilinear weight ---------------------------------------
-    for (int i = tid; i < NC * WS / 4; i += kThreads) reinterpret_cast<float4*>(GW)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    __syncthreads();
-    // Column `slot` of W belongs to the 8 lanes of the query.  At one step the 4 corner lanes of a half hit 4
-    // distinct cells, so a plain read-modify-write is safe; the two halves take turns (their points may share
-    // a cell), and the LDS pipe keeps consecutive steps of a wave in order.  (LDS float atomics instead of the 32
-    // dependent round trips: 490 -> 726 us per launch, ds_add_f32 is far slower than the read + write it replaces.)
-#pragma unroll
-    for (int hsel = 0; hsel < 2; ++hsel) {
-#pragma unroll
-      for (int k = 0; k < EPT; ++k) {
-        if (half == hsel && e_cell[k] >= 0) GW[e_cell[k] * WS + slot] += e_w[k];
-        asm volatile("" ::: "memory");
-      }
-    }
-    // corners outside the window.  As the boxes grow with training these stop being rare, and 32 float atomics per corner
-    // are a cliff (2 x 35 344 queries with boxes 3x their anchors: 0.67 -> 39.8 ms per launch).  With the binned path
-    // (`cursor`: the launch code counted these corners per (cell, head) row and scanned the counts) a corner is ONE
-    // 8-byte entry (grad_out row, weight) that box_bin_reduce_kernel sums per row after this kernel.
-#pragma unroll
-    for (int k = 0; k < EPT; ++k) {
-      if (e_cell[k] == -2) {
-        const int pi = half + 2 * k;
-        const BoxPx px = box_point(g, k_s[pi * 2], k_s[pi * 2 + 1], Hm, Wm);
-        const int cy = (int)floorf(px.h_im) + (corner >> 1), cx = (int)floorf(px.w_im) + (corner & 1);
-        const long long bin = ((long long)bi * S + (long long)cy * Wm + cx) * dm.h + m;
-        if (cursor) {
-          bin_push(cursor, bin_end, overflow, entries, bin, (int)t, e_w[k]);
-        } else {
-          float* gv = grad_value + bin * D;
-#pragma unroll 1
-          for (int c = 0; c < D; ++c) unsafeAtomicAdd(gv + c, e_w[k] * GOs[slot * VS + c]);
-        }
-      }
-    }
-    __syncthreads();
-
-    // ---- S5: GV = W . GO, flushed with one atomic per touched (cell, channel) -------------------------------
-    {
-      const int r16 = lane & 15, kk = lane >> 4;
-      constexpr int CBW = B::CBW;   // 16-cell blocks of W per wave
-      f32x4 acc[CBW][2];
-#pragma unroll
-      for (int i = 0; i < CBW; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      // coloured launch: the window's current contents, requested BEFORE the product so that the read half of the
-      // read-modify-write flush is hidden behind the MFMAs
-      float cur[CBW][2][4];
-      if (color >= 0) {
-#pragma unroll
-        for (int i = 0; i < CBW; ++i)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int cell = 16 * (CBW * wave + i) + 4 * kk + r;
-            const int cy = min(max(wy0 + cell / WINX, 0), Hm - 1), cx = min(max(wx0 + cell % WINX, 0), Wm - 1);
-            const float* gv = grad_value + (((long long)bi * S + (long long)cy * Wm + cx) * dm.h + m) * D + r16;
-            cur[i][0][r] = gv[0];
-            cur[i][1][r] = gv[16];
-          }
-      }
-      const float* ap = GW + (16 * (CBW * wave) + r16) * WS + kk;
-      const float* bp = GOs + kk * VS + r16;
-#pragma unroll
-      for (int ks = 0; ks < NQ / 4; ++ks) {
-        const float b0 = bp[4 * ks * VS], b1 = bp[4 * ks * VS + 16];
-#pragma unroll
-        for (int i = 0; i < CBW; ++i) {
-          const float av = ap[i * 16 * WS + 4 * ks];
-          acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b0, acc[i][0], 0, 0, 0);
-          acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b1, acc[i][1], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < CBW; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int cell = 16 * (CBW * wave + i) + 4 * kk + r;
-          const int cy = wy0 + cell / WINX, cx = wx0 + cell % WINX;
-          if (cy >= 0 && cy < Hm && cx >= 0 && cx < Wm) {
-            float* gv = grad_value + (((long long)bi * S + (long long)cy * Wm + cx) * dm.h + m) * D + r16;
-            if (color >= 0) {   // nobody else touches this window during this launch
-              if (acc[i][0][r] != 0.0f) gv[0] = __fadd_rn(cur[i][0][r], acc[i][0][r]);
-              if (acc[i][1][r] != 0.0f) gv[16] = __fadd_rn(cur[i][1][r], acc[i][1][r]);
-            } else {
-              if (acc[i][0][r] != 0.0f) unsafeAtomicAdd(gv, acc[i][0][r]);
-              if (acc[i][1][r] != 0.0f) unsafeAtomicAdd(gv + 16, acc[i][1][r]);
-            }
-          }
-        }
-    }
-  }  // tile loop
-}
-
-// ---- the same backward as TWO kernels (round 6) -------------------------------------------------------------------------------
-// box_bwd_tile_kernel holds, per 4 x 8-query tile, the value window, the grad_out tile, G / W, two softmax tables AND the
-// (cell, weight) pairs of pass A for pass B in registers: 256 VGPRs + 68 KB of LDS = two waves per SIMD, which issue a third
-// of their life (SQ counters, profiles/r05c_pmc_box_bwd_tile_*.txt): latency-bound, and three re-mappings of the same tile
-// did not change that.  Split along its only internal boundary, each half fits FOUR waves per SIMD:
-//   box_bwd_tile_a_kernel  S0 + S1 + pass A: G = GO . V^T, gradients of the offsets and logits.  G is written over the value
-//                          window (every wave holds its G blocks in registers until all reads of V are done): 40 KB of LDS.
-//                          No colour classes -- it writes nothing that overlaps -- so ONE launch over all tiles.
-//   box_bwd_tile_b_kernel  softmax + geometry again (a few hundred VALU instructions per tile against two fewer waves), the
-//                          W scatter in the order of the one-kernel form, GV = W . GO, window flush: 37 KB of LDS; per
-//                          colour class (plain read-modify-write) or one launch with atomics, as before.
-// Same arithmetic in the same order per element: grad_value / grad_offsets / grad_logits are the one-kernel form's bit for bit
-// (tests/test_box_fused_gpu.py::test_split_backward_bits_equal_one_kernel).  EFG_BOX_SPLIT=0: the one-kernel form (A/B).
-namespace bt {
-template <int TQY>
-constexpr size_t lds_bytes_a() {
-  using B = BT<TQY>;
-  constexpr int kVG = (B::NC * B::VS > B::NQ * B::GS) ? B::NC * B::VS : B::NQ * B::GS;
-  return sizeof(float) * (kVG + B::NQ * B::VS + 2 * B::NQ * PMAX + 2 * PMAX);
-}
-template <int TQY>
-constexpr size_t lds_bytes_b() {
-  using B = BT<TQY>;
-  return sizeof(float) * (B::NC * B::WS + B::NQ * B::VS + B::NQ * PMAX + 2 * PMAX);
-}
-}  // namespace bt
-
-template <int TQY>
-__global__ void __launch_bounds__(BT<TQY>::kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
-box_bwd_tile_a_kernel(const float* __restrict__ value, const long long* __restrict__ shapes, const float* __restrict__ ref,
-                      const float* __restrict__ off, const float* __restrict__ logits, const float* __restrict__ kidx,
-                      const float* __restrict__ grad_out, BoxDims dm, float* __restrict__ grad_off,
-                      float* __restrict__ grad_logits, int* __restrict__ counts, unsigned* __restrict__ absmax) {
-  // counts / absmax (both or neither): what box_bin_count_kernel and absmax_bits_kernel compute for the binned far corners,
-  // taken along -- this pass classifies every corner with the test pass B pushes with and reads every grad_out row once
-  using B = BT<TQY>;
-  constexpr int TQX = B::TQX, R = B::R, WINY = B::WINY, WINX = B::WINX, NQ = B::NQ, NC = B::NC, D = B::D, VS = B::VS, GS = B::GS,
-                kThreads = B::kThreads, PMAX = bt::PMAX;
-  unsigned go_max = 0u;
-  constexpr int kVG = (NC * VS > NQ * GS) ? NC * VS : NQ * GS;
-  extern __shared__ float lds[];
-  float* VG = lds;                     // V [NC][VS] in S0 / S1, then G [NQ][GS]
-  float* GOs = VG + kVG;               // [NQ][VS]
-  float* a_s = GOs + NQ * VS;          // [NQ][PMAX] un-normalised softmax weights
-  float* ga_s = a_s + NQ * PMAX;       // [NQ][PMAX]
-  float* k_s = ga_s + NQ * PMAX;       // [PMAX][2]
-  const int Hm = (int)shapes[0], Wm = (int)shapes[1];
-  if ((long long)Hm * Wm != dm.s) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid < 2 * dm.p) k_s[tid] = kidx[tid];
-  const int slot = tid >> 3, sub = tid & 7, corner = sub & 3, half = sub >> 2;
-  const int m = blockIdx.y, bi = blockIdx.z;
-  const int np = dm.p;
   const int tiles_x = (Wm + TQX - 1) / TQX, tiles_y = (Hm + TQY - 1) / TQY;
   const int ntiles = tiles_x * tiles_y;
   const long long S = dm.s;
-  constexpr int VPT = NC * (D / 4) / kThreads;
-  constexpr int EPT = PMAX / 2;
+  constexpr int VPT = NC * (D / 4) / kThreads;  // float4 of the value window per thread
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int ty0 = (tile / tiles_x) * TQY, tx0 = (tile % tiles_x) * TQX;
     const int wy0 = ty0 - R, wx0 = tx0 - R;
@@ -925,60 +640,27 @@ box_bwd_tile_a_kernel(const float* __restrict__ value, const long long* __restri
     }
     const int qy = ty0 + slot / TQX, qx = tx0 + slot % TQX;
     const bool qok = qy < Hm && qx < Wm;
-    const long long bqs = qok ? ((long long)bi * dm.lq + (long long)qy * Wm + qx) : 0;
-    const long long t = bqs * dm.h + m;
-    {
-      const int qyc = min(qy, Hm - 1), qxc = min(qx, Wm - 1);
-      const long long bqc = (long long)bi * dm.lq + (long long)qyc * Wm + qxc;
-      const float4 go = ld4(grad_out + (bqc * dm.h + m) * D + sub * 4);
-      *reinterpret_cast<float4*>(GOs + slot * VS + sub * 4) = qok ? go : make_float4(0.f, 0.f, 0.f, 0.f);
-      if (qok) {
-        go_max = max(max(go_max, __float_as_uint(go.x) & 0x7fffffffu), __float_as_uint(go.y) & 0x7fffffffu);
-        go_max = max(max(go_max, __float_as_uint(go.z) & 0x7fffffffu), __float_as_uint(go.w) & 0x7fffffffu);
-      }
+    const QueryRow q = load_query_row(ref, off, logits, grad_out, dm, Hm, Wm, bi, m, qy, qx, qok, sub, GOs + slot * VS + sub * 4);
+    if (qok) {
+      go_max = max(max(go_max, __float_as_uint(q.go.x) & 0x7fffffffu), __float_as_uint(q.go.y) & 0x7fffffffu);
+      go_max = max(max(go_max, __float_as_uint(q.go.z) & 0x7fffffffu), __float_as_uint(q.go.w) & 0x7fffffffu);
     }
-    float lgv[4], rf[5], of[5];
-    {
-      const int qyc = min(qy, Hm - 1), qxc = min(qx, Wm - 1);
-      const long long bqc = (long long)bi * dm.lq + (long long)qyc * Wm + qxc;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) lgv[k] = logits[bqc * dm.lg_rs + m * np + min(sub + 8 * k, np - 1)];
-      const float* r = ref + bqc * 7;
-      rf[0] = r[0], rf[1] = r[1], rf[2] = r[3], rf[3] = r[4], rf[4] = r[6];
-#pragma unroll
-      for (int k = 0; k < 5; ++k) of[k] = off[bqc * dm.off_rs + m * dm.v + min(k, dm.v - 1)];
-    }
+    const long long bqs = qok ? q.bq : 0;   // the row this query WRITES (a query past the edge writes nothing)
     float* as = a_s + slot * PMAX;
-    float mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (sub + 8 * k < np) mx = fmaxf(mx, lgv[k]);
-#pragma unroll
-    for (int dlt = 4; dlt > 0; dlt >>= 1) mx = fmaxf(mx, __shfl_xor(mx, dlt, 64));
-    float den = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (sub + 8 * k < np) {
-        const float ex = expf(lgv[k] - mx);
-        as[sub + 8 * k] = ex;
-        den += ex;
-      }
-#pragma unroll
-    for (int dlt = 4; dlt > 0; dlt >>= 1) den += __shfl_xor(den, dlt, 64);
-    const float inv = 1.0f / den;
-    const BoxGeo g = make_box_v(rf, of, dm.v);
+    const float inv = softmax_stats8(q.lgv, sub, np, as);
+    const BoxGeo g = make_box_v(q.rf, q.of, dm.v);
     __syncthreads();
 
     // ---- S1: G = GO . V^T, the wave's blocks kept in registers until every wave has read its part of V --------------
     {
-      const int mb = wave / B::WPM, nb0 = (wave % B::WPM) * B::NBW;
+      const int mb = wave / BT::WPM, nb0 = (wave % BT::WPM) * BT::NBW;
       const int r16 = lane & 15, kk = lane >> 4;
       float a[8];
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks) a[ks] = GOs[(16 * mb + r16) * VS + 4 * ks + kk];
-      f32x4 acc[B::NBW];
+      f32x4 acc[BT::NBW];
 #pragma unroll
-      for (int nbi = 0; nbi < B::NBW; nbi += 2) {
+      for (int nbi = 0; nbi < BT::NBW; nbi += 2) {
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
         const float* b0 = VG + (16 * (nb0 + nbi) + r16) * VS + kk;
         const float* b1 = b0 + 16 * VS;
@@ -992,31 +674,25 @@ box_bwd_tile_a_kernel(const float* __restrict__ value, const long long* __restri
       }
       __syncthreads();   // V is dead: G goes over it
 #pragma unroll
-      for (int nbi = 0; nbi < B::NBW; ++nbi)
+      for (int nbi = 0; nbi < BT::NBW; ++nbi)
 #pragma unroll
         for (int r = 0; r < 4; ++r) VG[(16 * mb + 4 * kk + r) * GS + 16 * (nb0 + nbi) + r16] = acc[nbi][r];
     }
     __syncthreads();
 
-    // ---- S2 (pass A), as in box_bwd_tile_kernel -----------------------------------------------------------------
+    // ---- S2: this lane = (query, corner, half of the lattice).  Gradients wrt the attention weights and the sampling
+    // locations come from 4 scalars of G per point
     float dcx = 0.f, dcy = 0.f, dw = 0.f, dh = 0.f, dth = 0.f, dot = 0.f;
     const int cyo = corner >> 1, cxo = corner & 1;
 #pragma unroll 1
     for (int j = 0; j < EPT / 4; ++j) {
-      const int op = half + 2 * (4 * j + corner);
-      const bool own = qok && op < np;
-      const float kxn = own ? k_s[op * 2] : 0.f, kyn = own ? k_s[op * 2 + 1] : 0.f;
-      const BoxPx px = box_point(g, kxn, kyn, Hm, Wm);
-      const float wgt = own ? as[op] * inv : 0.f;
-      const float h_im = px.h_im, w_im = px.w_im;
-      const bool inside = own && (h_im > -1.f) && (w_im > -1.f) && (h_im < (float)Hm) && (w_im < (float)Wm);
-      const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
-      const float lh = h_im - (float)h_low, lwf = w_im - (float)w_low;
-      const int h_pub = inside ? h_low : -(1 << 20);
-      float gq[4] = {0.f, 0.f, 0.f, 0.f};
+      const int op = half + 2 * (4 * j + corner);   // the point this lane owns in group j
+      const TilePoint pt = tile_point(g, k_s, as, inv, op, qok, np, Hm, Wm);
+      const float kxn = pt.kxn, kyn = pt.kyn, wgt = pt.wgt, lh = pt.lh, lwf = pt.lwf;
+      float gq[4] = {0.f, 0.f, 0.f, 0.f};              // G at the 4 corners of the OWN point
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const int hb = quad_bcast_i(h_pub, c), wb = quad_bcast_i(w_low, c);
+        const int hb = quad_bcast_i(pt.h_pub, c), wb = quad_bcast_i(pt.w_low, c);
         const int cy = hb + cyo, cx = wb + cxo;
         const bool ok = (unsigned)cy < (unsigned)Hm && (unsigned)cx < (unsigned)Wm;
         const int ly = cy - wy0, lx = cx - wx0;
@@ -1026,6 +702,7 @@ box_bwd_tile_a_kernel(const float* __restrict__ value, const long long* __restri
           if (in_win) {
             gval = VG[slot * GS + ly * WINX + lx];
           } else {  // the box has grown out of the window: dot product against the global value row
+            // (rare on a fresh model, common once the boxes have grown: 16-byte loads, the same 32 additions in order)
             const long long cellrow = ((long long)bi * S + (long long)cy * Wm + cx) * dm.h + m;
             if (counts) atomicAdd(counts + cellrow, 1);   // one entry of pass B in the bin of this (cell, head) row
             const float4* vr = reinterpret_cast<const float4*>(value + cellrow * D);
@@ -1045,18 +722,20 @@ box_bwd_tile_a_kernel(const float* __restrict__ value, const long long* __restri
       }
       const float g0 = gq[0], g1 = gq[1], g2 = gq[2], g3 = gq[3];
       const float hh = 1.f - lh, hw = 1.f - lwf;
-      const float gx = px.gx, gy = px.gy;
+      const float gx = pt.px.gx, gy = pt.px.gy;
       const float ga = fmaf(lh * lwf, g3, fmaf(lh * hw, g2, fmaf(hh * lwf, g1, hh * hw * g0)));
       const float gwl = (float)Wm * wgt * fmaf(hh, g1 - g0, lh * (g3 - g2));
       const float ghl = (float)Hm * wgt * fmaf(hw, g2 - g0, lwf * (g3 - g1));
+      // chain rule through grid = centre + R(theta) . (k * size)
       dcx += gwl;
       dcy += ghl;
       dw += kxn * (gwl * g.cs + ghl * g.sn);
       dh += kyn * (ghl * g.cs - gwl * g.sn);
       dth += gwl * (-(gx * g.sn) - gy * g.cs) + ghl * (gx * g.cs - gy * g.sn);
       dot = fmaf(wgt, ga, dot);
-      if (own) ga_s[slot * PMAX + op] = ga;
+      if (pt.own) ga_s[slot * PMAX + op] = ga;
     }
+    // every lane holds the sums over its own points: 4 corner lanes of a half, then the two halves 4 lanes apart
     dcx = quad_sum(dcx);
     dcy = quad_sum(dcy);
     dw = quad_sum(dw);
@@ -1078,9 +757,9 @@ box_bwd_tile_a_kernel(const float* __restrict__ value, const long long* __restri
       if (dm.v == 5) go[4] = dth * (2.0f * 3.14159274f / 16.0f);
     }
     __syncthreads();  // ga_s complete
+    // softmax backward: d logit_p = a_p * (ga_p - sum_j a_j ga_j)
     if (qok)
       for (int e = sub; e < np; e += 8) grad_logits[bqs * dm.lg_rs + m * np + e] = as[e] * inv * (ga_s[slot * PMAX + e] - dot);
-    (void)t;
   }
   if (absmax) {   // the largest |grad_out| this workgroup has seen: one atomic per wave (box_bin_reduce_kernel takes the max of the slots)
 #pragma unroll
@@ -1090,15 +769,18 @@ box_bwd_tile_a_kernel(const float* __restrict__ value, const long long* __restri
   }
 }
 
-template <int TQY>
-__global__ void __launch_bounds__(BT<TQY>::kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
+// ---- pass B: W scatter, GV = W . GO, window flush ----------------------------------------------------------------------------
+// color >= 0: this launch works on the tiles (ty, tx) with (ty % NCY, tx % NCX) == (color / NCX, color % NCX) only.  Their
+// windows never overlap, so the window flush is a plain read-modify-write and the NCY * NCX launches apply the overlapping
+// windows' contributions to a cell in a FIXED order: grad_value is reproducible bit for bit.  color < 0: one launch over all
+// tiles, float atomics.
+__global__ void __launch_bounds__(BT::kThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
 box_bwd_tile_b_kernel(const long long* __restrict__ shapes, const float* __restrict__ ref, const float* __restrict__ off,
                       const float* __restrict__ logits, const float* __restrict__ kidx, const float* __restrict__ grad_out,
                       BoxDims dm, float* __restrict__ grad_value, int* __restrict__ cursor, int2* __restrict__ entries,
                       const int* __restrict__ bin_end, int* __restrict__ overflow, int color) {
-  using B = BT<TQY>;
-  constexpr int TQX = B::TQX, R = B::R, WINY = B::WINY, WINX = B::WINX, NQ = B::NQ, NC = B::NC, D = B::D, VS = B::VS, WS = B::WS,
-                kThreads = B::kThreads, PMAX = bt::PMAX;
+  constexpr int TQY = BT::TQY, TQX = BT::TQX, R = BT::R, WINY = BT::WINY, WINX = BT::WINX, NQ = BT::NQ, NC = BT::NC, D = BT::D,
+                VS = BT::VS, WS = BT::WS, kThreads = BT::kThreads, PMAX = BT::PMAX, EPT = BT::EPT, NCY = BT::NCY, NCX = BT::NCX;
   extern __shared__ float lds[];
   float* Wl = lds;                     // W [NC][WS]
   float* GOs = Wl + NC * WS;           // [NQ][VS]
@@ -1112,13 +794,11 @@ box_bwd_tile_b_kernel(const long long* __restrict__ shapes, const float* __restr
   const int m = blockIdx.y, bi = blockIdx.z;
   const int np = dm.p;
   const int tiles_x = (Wm + TQX - 1) / TQX, tiles_y = (Hm + TQY - 1) / TQY;
-  constexpr int NCY = (WINY + TQY - 1) / TQY, NCX = (WINX + TQX - 1) / TQX;   // colour classes, as in box_bwd_tile_kernel
   const int cy0 = color >= 0 ? color / NCX : 0, cx0 = color >= 0 ? color % NCX : 0;
   const int sy_ = color >= 0 ? NCY : 1, sx_ = color >= 0 ? NCX : 1;
-  const int ctx = (tiles_x - cx0 + sx_ - 1) / sx_, cty = (tiles_y - cy0 + sy_ - 1) / sy_;
+  const int ctx = (tiles_x - cx0 + sx_ - 1) / sx_, cty = (tiles_y - cy0 + sy_ - 1) / sy_;   // tiles of this launch
   const int ntiles = max(ctx, 0) * max(cty, 0);
   const long long S = dm.s;
-  constexpr int EPT = PMAX / 2;
   for (int tj = blockIdx.x; tj < ntiles; tj += gridDim.x) {
     const int tile = (cy0 + sy_ * (tj / ctx)) * tiles_x + cx0 + sx_ * (tj % ctx);
     const int ty0 = (tile / tiles_x) * TQY, tx0 = (tile % tiles_x) * TQX;
@@ -1126,66 +806,27 @@ box_bwd_tile_b_kernel(const long long* __restrict__ shapes, const float* __restr
     __syncthreads();  // the previous tile's GEMM is done with GOs / W
     const int qy = ty0 + slot / TQX, qx = tx0 + slot % TQX;
     const bool qok = qy < Hm && qx < Wm;
-    const int qyc = min(qy, Hm - 1), qxc = min(qx, Wm - 1);
-    const long long bqc = (long long)bi * dm.lq + (long long)qyc * Wm + qxc;
-    const long long t = bqc * dm.h + m;   // (only used when qok)
-    {
-      const float4 go = ld4(grad_out + t * D + sub * 4);
-      *reinterpret_cast<float4*>(GOs + slot * VS + sub * 4) = qok ? go : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float lgv[4], rf[5], of[5];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) lgv[k] = logits[bqc * dm.lg_rs + m * np + min(sub + 8 * k, np - 1)];
-    {
-      const float* r = ref + bqc * 7;
-      rf[0] = r[0], rf[1] = r[1], rf[2] = r[3], rf[3] = r[4], rf[4] = r[6];
-#pragma unroll
-      for (int k = 0; k < 5; ++k) of[k] = off[bqc * dm.off_rs + m * dm.v + min(k, dm.v - 1)];
-    }
+    const QueryRow q = load_query_row(ref, off, logits, grad_out, dm, Hm, Wm, bi, m, qy, qx, qok, sub, GOs + slot * VS + sub * 4);
+    const long long t = q.bq * dm.h + m;   // the grad_out row (only used when qok)
     for (int i = tid; i < NC * WS / 4; i += kThreads) reinterpret_cast<float4*>(Wl)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     float* as = a_s + slot * PMAX;
-    float mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (sub + 8 * k < np) mx = fmaxf(mx, lgv[k]);
-#pragma unroll
-    for (int dlt = 4; dlt > 0; dlt >>= 1) mx = fmaxf(mx, __shfl_xor(mx, dlt, 64));
-    float den = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (sub + 8 * k < np) {
-        const float ex = expf(lgv[k] - mx);
-        as[sub + 8 * k] = ex;
-        den += ex;
-      }
-#pragma unroll
-    for (int dlt = 4; dlt > 0; dlt >>= 1) den += __shfl_xor(den, dlt, 64);
-    const float inv = 1.0f / den;
-    const BoxGeo g = make_box_v(rf, of, dm.v);
+    const float inv = softmax_stats8(q.lgv, sub, np, as);
+    const BoxGeo g = make_box_v(q.rf, q.of, dm.v);
     __syncthreads();
 
-    // ---- the (cell, weight) of this lane's corner of every point, exactly as pass A of the one-kernel form computes them
+    // ---- the (cell, weight) of this lane's corner of every point, classified exactly as in pass A
     int e_cell[EPT];    // window cell (>= 0), -1: nothing to add, -2: outside the window (binned / global path)
     float e_w[EPT];
     const int cyo = corner >> 1, cxo = corner & 1;
     const float sy = cyo ? 1.f : -1.f, ay = cyo ? 0.f : 1.f, sx = cxo ? 1.f : -1.f, ax = cxo ? 0.f : 1.f;
 #pragma unroll
     for (int j = 0; j < EPT / 4; ++j) {
-      const int op = half + 2 * (4 * j + corner);
-      const bool own = qok && op < np;
-      const float kxn = own ? k_s[op * 2] : 0.f, kyn = own ? k_s[op * 2 + 1] : 0.f;
-      const BoxPx px = box_point(g, kxn, kyn, Hm, Wm);
-      const float wgt = own ? as[op] * inv : 0.f;
-      const float h_im = px.h_im, w_im = px.w_im;
-      const bool inside = own && (h_im > -1.f) && (w_im > -1.f) && (h_im < (float)Hm) && (w_im < (float)Wm);
-      const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
-      const float lh = h_im - (float)h_low, lwf = w_im - (float)w_low;
-      const int h_pub = inside ? h_low : -(1 << 20);
+      const TilePoint pt = tile_point(g, k_s, as, inv, half + 2 * (4 * j + corner), qok, np, Hm, Wm);
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const int k = 4 * j + c;
-        const int hb = quad_bcast_i(h_pub, c), wb = quad_bcast_i(w_low, c);
-        const float lhb = quad_bcast_f(lh, c), lwb = quad_bcast_f(lwf, c), wgb = quad_bcast_f(wgt, c);
+        const int hb = quad_bcast_i(pt.h_pub, c), wb = quad_bcast_i(pt.w_low, c);
+        const float lhb = quad_bcast_f(pt.lh, c), lwb = quad_bcast_f(pt.lwf, c), wgb = quad_bcast_f(pt.wgt, c);
         const int cy = hb + cyo, cx = wb + cxo;
         const bool ok = (unsigned)cy < (unsigned)Hm && (unsigned)cx < (unsigned)Wm;
         const int ly = cy - wy0, lx = cx - wx0;
@@ -1193,12 +834,13 @@ box_bwd_tile_b_kernel(const long long* __restrict__ shapes, const float* __restr
         e_cell[k] = -1;
         e_w[k] = 0.f;
         if (ok) {
+          // ((corner >> 1) ? lh : 1 - lh) * ((corner & 1) ? lw : 1 - lw): one rounding each, as the select form
           e_w[k] = wgb * (fmaf(sy, lhb, ay) * fmaf(sx, lwb, ax));
           e_cell[k] = in_win ? ly * WINX + lx : -2;
         }
       }
     }
-    // ---- S3 / S4: W[cell][q], the two halves in turn (box_bwd_tile_kernel: why plain read-modify-writes are safe) ------
+    // ---- S3 / S4: W[cell][q], the two halves in turn (plain read-modify-writes: see the head of this section) ------
 #pragma unroll
     for (int hsel = 0; hsel < 2; ++hsel) {
 #pragma unroll
@@ -1207,6 +849,7 @@ box_bwd_tile_b_kernel(const long long* __restrict__ shapes, const float* __restr
         asm volatile("" ::: "memory");
       }
     }
+    // far corners: one entry into the bin of the corner's (cell, head) row, or D float atomics without a workspace
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
       if (e_cell[k] == -2) {
@@ -1225,13 +868,15 @@ box_bwd_tile_b_kernel(const long long* __restrict__ shapes, const float* __restr
     }
     __syncthreads();
 
-    // ---- S5: GV = W . GO and the window flush, as in box_bwd_tile_kernel ---------------------------------------------
+    // ---- S5: GV = W . GO, flushed into the window's rows of grad_value ------------------------------------------------
     {
       const int r16 = lane & 15, kk = lane >> 4;
-      constexpr int CBW = B::CBW;
+      constexpr int CBW = BT::CBW;   // 16-cell blocks of W per wave
       f32x4 acc[CBW][2];
 #pragma unroll
       for (int i = 0; i < CBW; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+      // coloured launch: the window's current contents, requested BEFORE the product so that the read half of the
+      // read-modify-write flush is hidden behind the MFMAs
       float cur[CBW][2][4];
       if (color >= 0) {
 #pragma unroll
@@ -1265,7 +910,7 @@ box_bwd_tile_b_kernel(const long long* __restrict__ shapes, const float* __restr
           const int cy = wy0 + cell / WINX, cx = wx0 + cell % WINX;
           if (cy >= 0 && cy < Hm && cx >= 0 && cx < Wm) {
             float* gv = grad_value + (((long long)bi * S + (long long)cy * Wm + cx) * dm.h + m) * D + r16;
-            if (color >= 0) {
+            if (color >= 0) {   // nobody else touches this window during this launch
               if (acc[i][0][r] != 0.0f) gv[0] = __fadd_rn(cur[i][0][r], acc[i][0][r]);
               if (acc[i][1][r] != 0.0f) gv[16] = __fadd_rn(cur[i][1][r], acc[i][1][r]);
             } else {
@@ -1275,7 +920,7 @@ box_bwd_tile_b_kernel(const long long* __restrict__ shapes, const float* __restr
           }
         }
     }
-  }
+  }  // tile loop
 }
 
 // ---- binned grad_value (decoder) -------------------------------------------------------------------------
@@ -1288,11 +933,9 @@ box_bwd_tile_b_kernel(const long long* __restrict__ shapes, const float* __restr
 __global__ void __launch_bounds__(256)
 box_bin_count_kernel(const long long* __restrict__ shapes, const long long* __restrict__ starts,
                      const float* __restrict__ ref, const float* __restrict__ off, const float* __restrict__ kidx,
-                     BoxDims dm, int* __restrict__ counts, int outside_tile_window, int tqy) {
+                     BoxDims dm, int* __restrict__ counts) {
   // one thread per (query, head, level): the box (its trigonometry) once, then the P lattice points -- the same
-  // location arithmetic as the backward kernels (make_box / box_point).  outside_tile_window: queries are the cells of
-  // the (single) map and only the corners box_bwd_tile_kernel cannot keep in the window of the query's TQY x 8 tile are
-  // counted; a box that cannot reach outside its window -- nearly all of them -- costs nothing beyond make_box.
+  // location arithmetic as the backward kernel (make_box / box_point)
   const long long total = (long long)dm.b * dm.lq * dm.h * dm.l;
   const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
@@ -1302,26 +945,7 @@ box_bin_count_kernel(const long long* __restrict__ shapes, const long long* __re
   const long long bq = t / dm.h;
   const int bi = (int)(bq / dm.lq);
   const int H = (int)shapes[li * 2], W = (int)shapes[li * 2 + 1];
-  int wy0 = 0, wx0 = 0;
-  const int winy = tqy + 2 * bt::R, winx = bt::TQX + 2 * bt::R;
   const BoxGeo g = make_box(ref + bq * 7, off + bq * dm.off_rs + (m * dm.l + li) * dm.v, dm.v);
-  if (outside_tile_window) {
-    const int q = (int)(bq % dm.lq);
-    wy0 = (q / W) / tqy * tqy - bt::R;
-    wx0 = (q % W) / bt::TQX * bt::TQX - bt::R;
-    // the lattice offsets are below half a box side (|k| < 0.5) in each axis before the rotation, so no sampling point
-    // is further than (w + h) / 2 from the box centre in x or in y (w / 2 and h / 2 for an upright box); a box whose
-    // whole reach (+ the bilinear neighbour, + 0.01 cell: the per-point positions are rounded 4 more times, ~1e-4 cell
-    // at 200 cells) stays inside the window has nothing to count.  Centre and size come from the SAME make_box the
-    // backward kernel classifies with.
-    const bool upright = g.sn == 0.f;   // the encoder's boxes: no rotation at all, reach = half a side per axis
-    const float ex = upright ? 0.5f * g.w : 0.5f * (g.w + g.h), ey = upright ? 0.5f * g.h : 0.5f * (g.w + g.h);
-    const float bx = g.cx * (float)W - 0.5f, by = g.cy * (float)H - 0.5f;
-    const float rx = ex * (float)W + 0.01f, ry = ey * (float)H + 0.01f;
-    if (floorf(bx - rx) >= (float)wx0 && floorf(bx + rx) + 1.f <= (float)(wx0 + winx - 1) &&
-        floorf(by - ry) >= (float)wy0 && floorf(by + ry) + 1.f <= (float)(wy0 + winy - 1))
-      return;
-  }
   int* row = counts + ((long long)bi * dm.s + starts[li]) * dm.h + m;
   for (int pi = 0; pi < dm.p; ++pi) {
     const BoxPx px = box_point(g, kidx[pi * 2], kidx[pi * 2 + 1], H, W);
@@ -1331,10 +955,7 @@ box_bin_count_kernel(const long long* __restrict__ shapes, const long long* __re
 #pragma unroll
     for (int cn = 0; cn < 4; ++cn) {
       const int cy = h_low + (cn >> 1), cx = w_low + (cn & 1);
-      if (cy >= 0 && cy <= H - 1 && cx >= 0 && cx <= W - 1) {
-        if (outside_tile_window && (unsigned)(cy - wy0) < (unsigned)winy && (unsigned)(cx - wx0) < (unsigned)winx) continue;
-        atomicAdd(row + ((long long)cy * W + cx) * dm.h, 1);
-      }
+      if (cy >= 0 && cy <= H - 1 && cx >= 0 && cx <= W - 1) atomicAdd(row + ((long long)cy * W + cx) * dm.h, 1);
     }
   }
 }
@@ -1533,26 +1154,29 @@ int bin_scan(const BinPlan& pl, void* ws, hipStream_t st) {
   return EFG_OK;
 }
 
-// count_here = false: only the pointers and the memset -- the caller's pass A counts the corners and takes the largest
-// |grad_out| along (box_bwd_tile_a_kernel), then calls bin_scan
-int bin_prepare(const BinPlan& pl, void* ws, const long long* shapes, const long long* starts, const float* ref,
-                const float* off, const float* kidx, const BoxDims& dm, int outside_tile_window, int tqy, hipStream_t st,
-                int** offs, int** cursor, int2** entries, int** overflow, const float* grad_out, long long grad_out_floats,
-                bool count_here = true) {
+// the pointers into the workspace; flag block and counters zeroed (they are adjacent: one memset)
+int bin_reset(const BinPlan& pl, void* ws, hipStream_t st, int** offs, int** cursor, int2** entries, int** overflow) {
   char* base = static_cast<char*>(ws);
   *overflow = reinterpret_cast<int*>(base + pl.off_flag);
   *offs = reinterpret_cast<int*>(base + pl.off_offsets);
   *cursor = reinterpret_cast<int*>(base + pl.off_cursor);
   *entries = reinterpret_cast<int2*>(base + pl.off_entries);
-  // flag + offsets are adjacent: one memset
   EFG_HIP_TRY(hipMemsetAsync(base + pl.off_flag, 0, 256 + sizeof(int) * (size_t)(pl.nbins + 1), st));
-  if (!count_here) return EFG_OK;
+  return EFG_OK;
+}
+
+// decoder: bin_reset, the largest |grad_out|, every corner counted, the counts scanned.  (The encoder's pass A counts its far
+// corners and takes the largest |grad_out| along; its launch code calls bin_reset and bin_scan around it.)
+int bin_prepare(const BinPlan& pl, void* ws, const long long* shapes, const long long* starts, const float* ref,
+                const float* off, const float* kidx, const BoxDims& dm, hipStream_t st, int** offs, int** cursor,
+                int2** entries, int** overflow, const float* grad_out, long long grad_out_floats) {
+  if (int rc = bin_reset(pl, ws, st, offs, cursor, entries, overflow)) return rc;
   // words 1..63 of the (zeroed) flag block: largest |grad_out| of the call as float bits (the scale of box_bin_reduce_kernel)
   hipLaunchKernelGGL(absmax_bits_kernel, dim3((unsigned)std::min<long long>(std::max<long long>(ceil_div(grad_out_floats / 4, 2048), 1), 1024)),
                      dim3(256), 0, st, grad_out, grad_out_floats / 4, reinterpret_cast<unsigned*>(*overflow));
   const long long nboxes = (long long)dm.b * dm.lq * dm.h * dm.l;
   hipLaunchKernelGGL(box_bin_count_kernel, dim3((unsigned)ceil_div(nboxes, 256)), dim3(256), 0, st, shapes, starts, ref,
-                     off, kidx, dm, *offs, outside_tile_window, tqy);
+                     off, kidx, dm, *offs);
   EFG_LAUNCH_CHECK();
   return bin_scan(pl, ws, st);
 }
@@ -1642,64 +1266,39 @@ extern "C" int efg_box_attn_fused_backward_strided_f32(const float* value, const
     // encoder self-attention (queries on the value map): fp64 LDS window per 8x8 query tile.  H, W are
     // device-side, so the launch is sized for a square map and the kernel strides over the tiles.
     const int side = (int)std::ceil(std::sqrt((double)s));
-    // tile shape: 4 x 8 queries (the 8 x 8 tile of round 2 -- BT<8>, one workgroup per CU -- was retired in round 6)
-    constexpr int tqy = 4;
-    const unsigned tiles_sq = (unsigned)(((side + tqy - 1) / tqy) * ((side + 7) / 8));
-    // workgroups along x of the tile kernel: it strides over the tiles and fetches one tile ahead (64 x h x b workgroups,
-    // two rounds of the 512 resident ones: 507 -> 490 us against one workgroup per tile)
-    constexpr int gx_env = 0;
-    const unsigned tile_gx = std::min<unsigned>((unsigned)(gx_env > 0 ? gx_env : 64), tiles_sq);
-    if (l * p <= bt::PMAX) {
-      // corners that leave the tile's window are binned per (cell, head) row when a workspace is given (see the kernel)
+    const unsigned tiles_sq = (unsigned)(((side + BT::TQY - 1) / BT::TQY) * ((side + BT::TQX - 1) / BT::TQX));
+    // workgroups along x of the tile kernels: they stride over the tiles (64 x h x b workgroups: 507 -> 490 us against one
+    // workgroup per tile; a colour launch of pass B with 16: +1.1 ms, 32: +0.35 ms, 64: +0.1 ms per step against the atomic launch)
+    const unsigned tile_gx = std::min<unsigned>(64u, tiles_sq);
+    if (l * p <= BT::PMAX) {
+      // corners that leave the tile's window are binned per (cell, head) row when a workspace is given (see the kernels)
       const BinPlan pl = bin_plan(b, s, h, l, lq, p);
       hipStream_t st = (hipStream_t)stream;
       const bool binned = ws != nullptr && pl.nentries < (1ll << 31) && pl.nbins + 1 < (1ll << 31);
       int *cursor = nullptr, *offs = nullptr, *overflow = nullptr;
       int2* entries = nullptr;
-      // EFG_BOX_SPLIT (default 1): pass A and pass B as two kernels at four waves per SIMD (see box_bwd_tile_a_kernel);
-      // 0 = the one-kernel form.
-      const int split_env = getenv("EFG_BOX_SPLIT") ? atoi(getenv("EFG_BOX_SPLIT")) : 1;   // (read per call: tests flip it in-process)
-      const bool split = split_env != 0;
       if (binned) {
         EFG_CHECK_ARG(ws_bytes >= pl.bytes, "box_attn_fused backward: workspace too small (%zu < %zu)", ws_bytes, pl.bytes);
-        // split: pass A counts the out-of-window corners and takes the largest |grad_out| along (two launches less per call)
-        if (int rc = bin_prepare(pl, ws, (const long long*)shapes, (const long long*)level_start, ref_windows, offsets,
-                                 kernel_indices, dm, 1, tqy, st, &offs, &cursor, &entries, &overflow, grad_out,
-                                 (long long)dm.b * dm.lq * dm.h * dm.d, /*count_here=*/!split))
-          return rc;
+        if (int rc = bin_reset(pl, ws, st, &offs, &cursor, &entries, &overflow)) return rc;
       }
       // EFG_BOX_DETERMINISTIC (default 1): the tiles in NCY x NCX colour classes whose windows never overlap, one launch
       // per class with a plain read-modify-write flush -- grad_value is the same bits run to run (with the binned
       // out-of-window corners, whose reduction is order-independent).  0: one launch, float atomics.
       static const int det_env = getenv("EFG_BOX_DETERMINISTIC") ? atoi(getenv("EFG_BOX_DETERMINISTIC")) : 1;
       const bool colored = det_env != 0 && binned;
-      const int ncolors = colored ? ((BT<4>::WINY + 3) / 4) * ((BT<4>::WINX + BT<4>::TQX - 1) / BT<4>::TQX) : 1;
-      // (workgroups along x of a colour launch; measured 16: +1.1 ms, 32: +0.35 ms, 64: +0.1 ms per step against the atomic launch)
-      constexpr int cgx_env = 64;
-      const unsigned gx_launch = colored ? std::min<unsigned>(tile_gx, (unsigned)std::max(cgx_env, 1)) : tile_gx;
-      if (split) {
-        EFG_ALLOW_DYNAMIC_LDS(box_bwd_tile_a_kernel<4>, bt::lds_bytes_a<4>());
-        hipLaunchKernelGGL(box_bwd_tile_a_kernel<4>, dim3(tile_gx, h, b), dim3(BT<4>::kThreads), bt::lds_bytes_a<4>(), st, value,
-                           (const long long*)shapes, ref_windows, offsets, logits, kernel_indices, grad_out, dm, grad_offsets,
-                           grad_logits, binned ? offs : nullptr, binned ? reinterpret_cast<unsigned*>(overflow) : nullptr);
-        EFG_LAUNCH_CHECK();
-        if (binned)
-          if (int rc = bin_scan(pl, ws, st)) return rc;
-        EFG_ALLOW_DYNAMIC_LDS(box_bwd_tile_b_kernel<4>, bt::lds_bytes_b<4>());
-      }
-      for (int col = 0; col < ncolors; ++col) {
-        const int color = colored ? col : -1;
-        if (split) {
-          hipLaunchKernelGGL(box_bwd_tile_b_kernel<4>, dim3(gx_launch, h, b), dim3(BT<4>::kThreads), bt::lds_bytes_b<4>(), st,
-                             (const long long*)shapes, ref_windows, offsets, logits, kernel_indices, grad_out, dm, grad_value,
-                             cursor, entries, offs ? offs + 1 : nullptr, overflow, color);
-        } else {
-          EFG_ALLOW_DYNAMIC_LDS(box_bwd_tile_kernel<4>, bt::lds_bytes<4>());
-          hipLaunchKernelGGL(box_bwd_tile_kernel<4>, dim3(gx_launch, h, b), dim3(BT<4>::kThreads), bt::lds_bytes<4>(), st, value,
-                             (const long long*)shapes, ref_windows, offsets, logits, kernel_indices, grad_out, dm, grad_value,
-                             grad_offsets, grad_logits, cursor, entries, offs ? offs + 1 : nullptr, overflow, color);
-        }
-      }
+      const int ncolors = colored ? BT::NCY * BT::NCX : 1;
+      EFG_ALLOW_DYNAMIC_LDS(box_bwd_tile_a_kernel, BT::lds_bytes_a);
+      hipLaunchKernelGGL(box_bwd_tile_a_kernel, dim3(tile_gx, h, b), dim3(BT::kThreads), BT::lds_bytes_a, st, value,
+                         (const long long*)shapes, ref_windows, offsets, logits, kernel_indices, grad_out, dm, grad_offsets,
+                         grad_logits, binned ? offs : nullptr, binned ? reinterpret_cast<unsigned*>(overflow) : nullptr);
+      EFG_LAUNCH_CHECK();
+      if (binned)
+        if (int rc = bin_scan(pl, ws, st)) return rc;
+      EFG_ALLOW_DYNAMIC_LDS(box_bwd_tile_b_kernel, BT::lds_bytes_b);
+      for (int col = 0; col < ncolors; ++col)
+        hipLaunchKernelGGL(box_bwd_tile_b_kernel, dim3(tile_gx, h, b), dim3(BT::kThreads), BT::lds_bytes_b, st,
+                           (const long long*)shapes, ref_windows, offsets, logits, kernel_indices, grad_out, dm, grad_value,
+                           cursor, entries, offs ? offs + 1 : nullptr, overflow, colored ? col : -1);
       if (binned) {
         EFG_LAUNCH_CHECK();
         const unsigned blocks = (unsigned)std::min<long long>(ceil_div(pl.nbins, 32), 16384);
@@ -1724,7 +1323,7 @@ extern "C" int efg_box_attn_fused_backward_strided_f32(const float* value, const
     if (binned) {
       EFG_CHECK_ARG(ws_bytes >= pl.bytes, "box_attn_fused backward: workspace too small (%zu < %zu)", ws_bytes, pl.bytes);
       if (int rc = bin_prepare(pl, ws, (const long long*)shapes, (const long long*)level_start, ref_windows, offsets,
-                               kernel_indices, dm, 0, 8, st, &offs, &cursor, &entries, &overflow, grad_out,
+                               kernel_indices, dm, st, &offs, &cursor, &entries, &overflow, grad_out,
                                (long long)dm.b * dm.lq * dm.h * dm.d))
         return rc;
     } else if (ws != nullptr && ws_bytes >= sizeof(int)) {
