@@ -5,8 +5,8 @@
 // active sites, then ReLU, in the residual blocks `relu(bn(conv) + shortcut)`.  PyTorch runs that as 4 kernels
 // forward (statistics, running-stat update, transform, ReLU; + 1 for the residual add) and 3 backward, and its
 // channels-last statistics kernels reach 0.4 TB/s on these [M, 16..256] tensors.  Here:
-//   forward : bn_stats_kernel  -- per-workgroup (count, mean, M2) of a contiguous row chunk (two passes over the
-//                                 chunk: the second one hits L2)
+//   forward : bn_stats_kernel  -- per-workgroup (count, mean, M2, residual) of a contiguous row chunk (two passes
+//                                 over the chunk: the second one hits L2)
 //             bn_stats_merge   -- one wave per channel merges the chunks with Chan's formula and updates the running
 //                                 statistics
 //             bn_apply_kernel  -- y = relu((x - mean) * invstd * w + b + residual), float4 streaming
@@ -14,6 +14,17 @@
 //             bn_bwd_apply_kernel  (dx, and d residual = dy')
 // Lanes run over channels (float4) so every load is a coalesced row segment; reductions are deterministic (fixed
 // chunking and merge order).
+//
+// The chunk mean is an fp32 number, so the chunk's M2 = sum (x - mean)^2 is taken about a ROUNDED mean.  Chan's
+// between-chunk term n_a n_b / n (mean_b - mean_a)^2 is first order in that rounding: with x = 1000 +- 0.01 the
+// means are good to 1e-4 and differ by 3e-3, and the variance of 33 rows in two chunks came out 0.5 % off (a two-pass
+// variance: 1e-4).  The chunk therefore also reports its residual r = sum (x - mean) -- zero for an exact mean -- and
+// the merge works on corrected triples, all means as offsets from the first chunk's: e = (mean - mean_0) + r / n,
+// M2 - r^2 / n.  The offsets are small numbers with full relative precision; one rounding when mean_0 is added back.
+// The correction is applied where the mean is far from 0 against the spread, |mean| > 2^10 std (`far_mean`, from the
+// first chunk's mean and the counts and M2 of all chunks): from there on the uncorrected between-chunk term costs
+// the variance more than ten of its 24 bits.  Nearer to 0 the merge is left as it was, bit for bit: the rounding of
+// the chunk means is then small against the spread, and a training step's results do not move.
 #include "common.h"
 
 #include <algorithm>
@@ -56,16 +67,58 @@ __device__ __forceinline__ float4 quad_sum(float4 v, int q4, float4* smem) {
   return r;
 }
 
-// partial[b][0][c] = count (as float), [1] = mean, [2] = M2 of chunk b
+// the same for two values at once (one pair of barriers); smem: float4[512]
+__device__ __forceinline__ void quad_sum2(float4 a, float4 b, int q4, float4* smem, float4& ra, float4& rb) {
+  smem[threadIdx.x] = a;
+  smem[256 + threadIdx.x] = b;
+  __syncthreads();
+  ra = rb = make_float4(0.f, 0.f, 0.f, 0.f);
+  if ((int)threadIdx.x < q4) {
+    for (int t = threadIdx.x; t < 256; t += q4) {
+      const float4 o = smem[t], p = smem[256 + t];
+      ra.x += o.x;
+      ra.y += o.y;
+      ra.z += o.z;
+      ra.w += o.w;
+      rb.x += p.x;
+      rb.y += p.y;
+      rb.z += p.z;
+      rb.w += p.w;
+    }
+  }
+  __syncthreads();
+}
+
+// one chunk of the merge: (count, mean, M2 about that mean, residual sum (x - mean)) -> the mean as an offset from
+// `ref` and M2 about the exact chunk mean (see the head of the file)
+__device__ __forceinline__ void chunk_fix(bool on, float nb, float ref, float& mb, float& qb, float rb) {
+  if (!on) return;
+  const float inv = 1.0f / fmaxf(nb, 1.f);
+  mb = (mb - ref) + rb * inv;
+  qb = fmaxf(qb - rb * rb * inv, 0.f);
+}
+
+// Is the mean more than 2^10 std from 0?  One wave; n_sum, q_sum = the lane's share of the chunks' counts and M2
+// (summed over the wave here, every lane gets the same bits), mean0 = the mean of the first chunk (never empty).
+__device__ __forceinline__ bool far_mean(float n_sum, float q_sum, float mean0) {
+#pragma unroll
+  for (int dlt = 32; dlt > 0; dlt >>= 1) {
+    n_sum += __shfl_xor(n_sum, dlt, 64);
+    q_sum += __shfl_xor(q_sum, dlt, 64);
+  }
+  return mean0 * mean0 * n_sum > 1048576.f * q_sum;
+}
+
+// partial[b][0][c] = count (as float), [1] = mean, [2] = M2 about it, [3] = sum (x - mean) of chunk b
 __global__ void __launch_bounds__(256)
 bn_stats_kernel(const float* __restrict__ x, long long m, int c, float* __restrict__ partial) {
-  __shared__ float4 smem[256];
+  __shared__ float4 smem[512];
   const int q4 = c / 4, rstep = 256 / q4;
   const int cq = threadIdx.x % q4, r0 = threadIdx.x / q4;
   const bool lane_on = r0 < rstep;  // 256 % q4 may leave idle threads
   // blockIdx.y = sample for the per-sample statistics of GroupNorm (m rows each); BatchNorm launches one
   x += (long long)blockIdx.y * m * c;
-  partial += (long long)blockIdx.y * gridDim.x * 3 * c;
+  partial += (long long)blockIdx.y * gridDim.x * 4 * c;
   const Chunk ck = chunk_of(m, gridDim.x, blockIdx.x);
   const float n = (float)(ck.row_hi - ck.row_lo);
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -83,21 +136,28 @@ bn_stats_kernel(const float* __restrict__ x, long long m, int c, float* __restri
   __syncthreads();
   const float4 mu = smem[cq];
   __syncthreads();
-  float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 q = make_float4(0.f, 0.f, 0.f, 0.f), e = q;
   if (lane_on)
     for (long long r = ck.row_lo + r0; r < ck.row_hi; r += rstep) {
       const float4 v = ld4(x + r * c + cq * 4);
-      q.x += (v.x - mu.x) * (v.x - mu.x);
-      q.y += (v.y - mu.y) * (v.y - mu.y);
-      q.z += (v.z - mu.z) * (v.z - mu.z);
-      q.w += (v.w - mu.w) * (v.w - mu.w);
+      const float4 d = make_float4(v.x - mu.x, v.y - mu.y, v.z - mu.z, v.w - mu.w);
+      e.x += d.x;
+      e.y += d.y;
+      e.z += d.z;
+      e.w += d.w;
+      q.x += d.x * d.x;
+      q.y += d.y * d.y;
+      q.z += d.z * d.z;
+      q.w += d.w * d.w;
     }
-  const float4 m2 = quad_sum(q, q4, smem);
+  float4 m2, res;
+  quad_sum2(q, e, q4, smem, m2, res);
   if ((int)threadIdx.x < q4) {
-    float* p = partial + (long long)blockIdx.x * 3 * c + cq * 4;
+    float* p = partial + (long long)blockIdx.x * 4 * c + cq * 4;
     st4(p, make_float4(n, n, n, n));
     st4(p + c, mu);
     st4(p + 2 * c, m2);
+    st4(p + 3 * c, res);
   }
 }
 
@@ -108,22 +168,32 @@ bn_stats_merge_kernel(const float* __restrict__ partial, int nchunks, int c, flo
                       float* __restrict__ mean_out, float* __restrict__ invstd_out, float* __restrict__ running_mean,
                       float* __restrict__ running_var, long long* __restrict__ num_batches) {
   const int lane = threadIdx.x, ch = blockIdx.x;
+  float n_sum = 0.f, q_sum = 0.f;
+  for (int b = lane; b < nchunks; b += 64) {
+    n_sum += partial[(long long)b * 4 * c + ch];
+    q_sum += partial[(long long)b * 4 * c + 2 * c + ch];
+  }
+  const bool fix = far_mean(n_sum, q_sum, partial[c + ch]);
+  const float ref = fix ? partial[c + ch] : 0.f;  // the mean of chunk 0: all means below are offsets from it
   float cnt = 0.f, mean = 0.f, M2 = 0.f;
   // (the chunks of a lane are loaded four at a time and folded in the same order as before: a loop that loads, tests
   // and folds one chunk per trip pays one memory round trip per chunk)
   for (int b0 = lane; b0 < nchunks; b0 += 64 * 4) {
-    float nbv[4], mbv[4], qbv[4];
+    float nbv[4], mbv[4], qbv[4], rbv[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int b = b0 + 64 * u;
-      const float* p = partial + (long long)min(b, nchunks - 1) * 3 * c + ch;
+      const float* p = partial + (long long)min(b, nchunks - 1) * 4 * c + ch;
       nbv[u] = b < nchunks ? p[0] : 0.f;
       mbv[u] = p[c];
       qbv[u] = p[2 * c];
+      rbv[u] = p[3 * c];
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const float nb = nbv[u], mb = mbv[u], qb = qbv[u];
+      const float nb = nbv[u];
+      float mb = mbv[u], qb = qbv[u];
+      chunk_fix(fix, nb, ref, mb, qb, rbv[u]);
       if (nb > 0.f) {
         const float tot_n = cnt + nb, d = mb - mean;
         mean += d * (nb / tot_n);
@@ -151,6 +221,7 @@ bn_stats_merge_kernel(const float* __restrict__ partial, int nchunks, int c, flo
   }
   if (lane == 0) {
     const float var = cnt > 0.f ? M2 / cnt : 0.f;
+    mean += ref;
     mean_out[ch] = mean;
     invstd_out[ch] = 1.0f / sqrtf(var + eps);
     if (running_mean) {
@@ -282,22 +353,33 @@ __global__ void __launch_bounds__(64)
 gn_stats_merge_kernel(const float* __restrict__ partial, int nchunks, int c, int cpg, float eps,
                       float* __restrict__ mean_out, float* __restrict__ rstd_out) {
   const int lane = threadIdx.x, g = blockIdx.x, b = blockIdx.y, groups = c / cpg;
-  const float* base = partial + (long long)b * nchunks * 3 * c;
+  const float* base = partial + (long long)b * nchunks * 4 * c;
+  float n_sum = 0.f, q_sum = 0.f;
+  for (int i = lane; i < nchunks * cpg; i += 64) {
+    const float* p = base + (long long)(i / cpg) * 4 * c + g * cpg + i % cpg;
+    n_sum += p[0];
+    q_sum += p[2 * c];
+  }
+  const bool fix = far_mean(n_sum, q_sum, base[c + g * cpg]);
+  const float ref = fix ? base[c + g * cpg] : 0.f;  // the mean of the first (chunk, channel) item: the others as offsets
   float cnt = 0.f, mean = 0.f, M2 = 0.f;
   const int items = nchunks * cpg;
   for (int i0 = lane; i0 < items; i0 += 64 * 8) {   // eight items in flight per lane, folded in the same order
-    float nbv[8], mbv[8], qbv[8];
+    float nbv[8], mbv[8], qbv[8], rbv[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int i = min(i0 + 64 * u, items - 1);
-      const float* p = base + (long long)(i / cpg) * 3 * c + g * cpg + i % cpg;
+      const float* p = base + (long long)(i / cpg) * 4 * c + g * cpg + i % cpg;
       nbv[u] = (i0 + 64 * u < items) ? p[0] : 0.f;
       mbv[u] = p[c];
       qbv[u] = p[2 * c];
+      rbv[u] = p[3 * c];
     }
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      const float nb = nbv[u], mb = mbv[u], qb = qbv[u];
+      const float nb = nbv[u];
+      float mb = mbv[u], qb = qbv[u];
+      chunk_fix(fix, nb, ref, mb, qb, rbv[u]);
       if (nb > 0.f) {
         const float tot_n = cnt + nb, d = mb - mean;
         mean += d * (nb / tot_n);
@@ -324,7 +406,7 @@ gn_stats_merge_kernel(const float* __restrict__ partial, int nchunks, int c, int
     cnt = tot_n;
   }
   if (lane == 0) {
-    mean_out[b * groups + g] = mean;
+    mean_out[b * groups + g] = mean + ref;
     rstd_out[b * groups + g] = 1.0f / sqrtf((cnt > 0.f ? M2 / cnt : 0.f) + eps);
   }
 }
@@ -442,10 +524,10 @@ int nblocks_for(long long m) { return (int)std::max<long long>(1, std::min<long 
 
 using namespace efg;
 
-// workspace: partials [kBnBlocks][3][c] floats
+// workspace: partials [kBnBlocks][4][c] floats
 extern "C" size_t efg_bn_workspace_bytes(int c) {
   if (c < 1) return 0;
-  return align_up(sizeof(float) * 3 * (size_t)c * kBnBlocks, 256) + 256;
+  return align_up(sizeof(float) * 4 * (size_t)c * kBnBlocks, 256) + 256;
 }
 
 static int bn_check(int64_t m, int c) {
@@ -497,10 +579,10 @@ extern "C" int efg_bn_backward_f32(const float* dy, const float* x, const float*
 }
 
 // ---- GroupNorm (channels-last) --------------------------------------------------------------------------------
-// workspace: partials [batch][kBnBlocks][3][c] + sums [batch][2][c] + ab [batch][groups][2] floats
+// workspace: partials [batch][kBnBlocks][4][c] + sums [batch][2][c] + ab [batch][groups][2] floats
 extern "C" size_t efg_gn_workspace_bytes(int batch, int c) {
   if (batch < 1 || c < 1) return 0;
-  return align_up(sizeof(float) * ((size_t)batch * kBnBlocks * 3 * c + (size_t)batch * 4 * c), 256) + 256;
+  return align_up(sizeof(float) * ((size_t)batch * kBnBlocks * 4 * c + (size_t)batch * 4 * c), 256) + 256;
 }
 
 static int gn_check(int batch, int64_t rows, int c, int groups) {
@@ -539,7 +621,7 @@ extern "C" int efg_gn_backward_f32(const float* dy, const float* x, const float*
   hipStream_t st = (hipStream_t)stream;
   const int nb = nblocks_for(rows), cpg = c / groups;
   float* partial = static_cast<float*>(ws);
-  float* sums = partial + (size_t)batch * kBnBlocks * 3 * c;
+  float* sums = partial + (size_t)batch * kBnBlocks * 4 * c;
   float* ab = sums + (size_t)batch * 2 * c;
   hipLaunchKernelGGL(gn_bwd_reduce_kernel, dim3(nb, batch), dim3(256), 0, st, dy, x, mean, rstd, (long long)rows, c, cpg,
                      partial);

@@ -1,5 +1,7 @@
-"""Plain float64 references for the sparse convolution, the fused box attention and the detection-loss tail (matching
-cost, focal loss, box loss), and an element-wise error bar.
+"""Plain float64 references for the sparse convolution, the fused box attention, the detection-loss tail (matching
+cost, focal loss, box loss) and the normalisation kernels (BatchNorm (+ residual) (+ ReLU) with its running statistics,
+channels-last GroupNorm, residual-add + LayerNorm; written out from mean, biased variance and rstd, forward and backward),
+and an element-wise error bar.
 
 Nothing here imports efg_amd.spconv, the oracle or a HIP entry point: the rulebook is rebuilt from the int32 site
 coordinates with torch.sort / searchsorted, the products are torch float64 matmuls, and the box-attention sampling is
@@ -532,3 +534,176 @@ def box_loss_fp64(boxes, tgt_boxes, l_idx, b_idx, q_idx, g_idx, denom, grad_out)
     rows[li, bi, qi] = True
     return dict(loss=loss, loss_mag=loss.clone(), loss_n=count.view(nl, 1) * torch.tensor([6.0, 1.0, 1.0], dtype=torch.float64, device=dev),
                 loss_cond=loss_cond, grad=rows_of(gsrc), grad_mag=rows_of(g_mag), grad_n=1, grad_cond=rows_of(g_cond), rows=rows)
+
+
+# ---- normalisation: BatchNorm (+ residual) (+ ReLU), GroupNorm, residual-add + LayerNorm (csrc/batchnorm.hip, layernorm.hip) --
+# One operation with three reduction sets, written out: mu = mean(x), var = mean((x - mu)^2) (biased), rstd = (var + eps)^-1/2,
+# xhat = (x - mu) rstd, y = relu?(xhat w + b + residual); backward, with dy' = dy [y > 0] and g = w dy':
+#   dx = rstd (g - mean(g) - xhat mean(g xhat)),  d residual = dy',  dw = sum dy' xhat,  db = sum dy'
+# (means over the statistics set of the element, sums over everything that shares the parameter).  Nothing of efg_amd and no
+# torch *_norm is used.  `_mag` is the same expression over absolute values, `_n` the number of terms summed into the element
+# (1 for y; the size of the statistics set for dx; the rows of a parameter for dw / db).  `_cond` is an ABSOLUTE allowance for
+# assert_elementwise's `geo64`: any fp32 evaluation rounds the two statistics, the mean by about sqrt(n) 2^-24 mean|x| (a sum of
+# n values) and rstd by a relative (sqrt(n) + 2) 2^-24 (the variance is a sum of n non-negative terms; + 2 for the square root
+# and the divide), and on top of that takes the variance about its ROUNDED mean, sum (x - mu')^2 = sum (x - mu)^2 + n (mu' - mu)^2,
+# which moves rstd by another relative d_mu^2 / (2 (var + eps)) -- second order, and the only term that matters when the data sit
+# far from 0 (x = 1000 +- 0.01).  `_cond` = |d out / d mu| d_mu + |d out / d rstd| d_rstd, taken in float64 with torch.func.jvp
+# of the written-out formula; one tangent holds all statistics at once because every element depends on exactly one of each
+# kind.  The Taylor terms of second order (1/2 |d2 / d mu2| d_mu^2 + |d2 / d mu d rstd| d_mu d_rstd + 1/2 |d2 / d rstd2| d_rstd^2,
+# nested jvp) are added: with x = 1000 +- 0.01 in a set of four, rstd d_mu reaches 1e-2, and where the first-order term of an
+# element happens to vanish the second-order one is still 1e-4 of the element, a hundred times the rounding bar.  For dw (db does not see the statistics) it is the sum of the per-term absolute sensitivities.  With it a constant
+# channel (var = 0, rstd = eps^-1/2) and a large offset are well-defined cases: the reference is 0 where fp32 is not.  It never
+# sees a kernel's output.
+# ReLU ties: an element whose float64 pre-activation lies within its own forward bound (at the cap c = NORM_TIE_C) of 0 may
+# take either side of y > 0.  `near_zero` marks them; dx and d residual of those elements are not compared, and what a flip
+# moves elsewhere -- sum_near_zero |dy| in db, |dy xhat| in dw, and the two means inside dx -- is added to `_cond`.
+NORM_TIE_C = 16.0
+
+
+def _norm_fp64(x, stat_dims, par_dims, w, b, res, eps, relu, dy):
+    """The core: x float64 of any rank, statistics over `stat_dims`, w and b broadcastable to x and constant over `par_dims`,
+    res like x or None, dy like x or None.  Returns a dict of float64 tensors (statistics with keepdim, dweight / dbias with
+    keepdim over par_dims)."""
+    n = 1
+    for d in stat_dims:
+        n *= x.shape[d]
+    n = max(n, 1)
+    mu = x.mean(stat_dims, keepdim=True)
+    var = ((x - mu) ** 2).mean(stat_dims, keepdim=True)
+    rstd = (var + eps) ** -0.5
+    d_mu = math.sqrt(n) * U32 * x.abs().mean(stat_dims, keepdim=True)
+    d_rs = rstd * ((math.sqrt(n) + 2) * U32 + 0.5 * d_mu ** 2 / (var + eps))
+    r0 = res if res is not None else torch.zeros((), dtype=x.dtype, device=x.device)
+
+    def sens(f):
+        """[|d out / d mu| d_mu + |d out / d rstd| d_rstd, carried to second order, for each output of f(mu, rstd)]"""
+        zm, zs = torch.zeros_like(mu), torch.zeros_like(rstd)
+        t_mu, t_rs = (d_mu, zs), (zm, d_rs)
+        along = lambda t: (lambda m, s: torch.func.jvp(f, (m, s), t)[1])   # noqa: E731
+        j_m, j_mm = torch.func.jvp(along(t_mu), (mu, rstd), t_mu)
+        j_s, j_ss = torch.func.jvp(along(t_rs), (mu, rstd), t_rs)
+        _, j_ms = torch.func.jvp(along(t_mu), (mu, rstd), t_rs)
+        return [a.abs() + b.abs() + 0.5 * aa.abs() + ab.abs() + 0.5 * bb.abs() for a, b, aa, ab, bb in zip(j_m, j_s, j_mm, j_ms, j_ss)]
+
+    def fwd(m, s):
+        return ((x - m) * s * w + b + r0,)
+
+    pre, = fwd(mu, rstd)
+    y_mag = (x - mu).abs() * rstd * w.abs() + b.abs() + r0.abs()
+    y_cond, = sens(fwd)
+    out = dict(mean=mu, var=var, rstd=rstd, d_mean=d_mu, d_rstd=d_rs, n_stat=n, y_mag=y_mag, y_n=1, y_cond=y_cond)
+    if relu:
+        near = pre.abs() <= NORM_TIE_C * U32 * y_mag + y_cond
+        mask = (pre > 0).to(x.dtype)
+        out.update(y=pre.clamp(min=0), near_zero=near)
+    else:
+        near = torch.zeros_like(pre, dtype=torch.bool)
+        mask = torch.ones_like(pre)
+        out.update(y=pre, near_zero=near)
+    out["near_zero_share"] = float(near.double().mean()) if near.numel() else 0.0
+    if dy is None:
+        return out
+    dyp = dy * mask
+    g = w * dyp
+
+    def bwd(m, s):
+        xh = (x - m) * s
+        return s * (g - g.mean(stat_dims, keepdim=True) - xh * (g * xh).mean(stat_dims, keepdim=True)), dyp * xh
+
+    dx, t = bwd(mu, rstd)
+    dx_cond, t_cond = sens(bwd)
+    xh = (x - mu) * rstd
+    ga = g.abs()
+    dx_mag = rstd * (ga + ga.mean(stat_dims, keepdim=True) + xh.abs() * (ga * xh.abs()).mean(stat_dims, keepdim=True))
+    dw_cond = t_cond.sum(par_dims, keepdim=True)
+    db_cond = torch.zeros_like(dw_cond)
+    if relu:
+        nz = near.to(x.dtype)
+        a1 = (nz * (w * dy).abs()).sum(stat_dims, keepdim=True) / n
+        a2 = (nz * (w * dy * xh).abs()).sum(stat_dims, keepdim=True) / n
+        dx_cond = dx_cond + rstd * (a1 + xh.abs() * a2)
+        dw_cond = dw_cond + (nz * (dy * xh).abs()).sum(par_dims, keepdim=True)
+        db_cond = db_cond + (nz * dy.abs()).sum(par_dims, keepdim=True)
+    n_par = 1
+    for d in par_dims:
+        n_par *= x.shape[d]
+    out.update(dx=dx, dx_mag=dx_mag, dx_n=n, dx_cond=dx_cond,
+               dresidual=dyp, dresidual_mag=dyp.abs(), dresidual_n=1, dresidual_cond=torch.zeros_like(dyp),
+               dweight=t.sum(par_dims, keepdim=True), dweight_mag=t.abs().sum(par_dims, keepdim=True), dweight_n=n_par,
+               dweight_cond=dw_cond,
+               dbias=dyp.sum(par_dims, keepdim=True), dbias_mag=dyp.abs().sum(par_dims, keepdim=True), dbias_n=n_par,
+               dbias_cond=db_cond)
+    return out
+
+
+_NORM_OUTS = ("y", "dx", "dresidual", "dweight", "dbias")
+
+
+def _norm_result(core, shape, par_shape, keep):
+    """Reshape the core's outputs: y / dx / dresidual to `shape`, dweight / dbias to `par_shape`; `keep` names the outputs."""
+    res = {"near_zero": core["near_zero"].reshape(shape), "near_zero_share": core["near_zero_share"]}
+    for k in keep:
+        if k not in core:
+            continue
+        shp = par_shape if k in ("dweight", "dbias") else shape
+        for t in ("", "_mag", "_cond"):
+            res[k + t] = core[k + t].reshape(shp)
+        res[k + "_n"] = core[k + "_n"]
+    return res
+
+
+def batchnorm_fp64(x, residual, w, b, running_mean, running_var, momentum, eps, relu, dy):
+    """relu?(BatchNorm(x) + residual?) in training mode over rows x [M, C], statistics per channel over the M rows, with its
+    gradients for the upstream dy (or None: forward only) and the updated running statistics: running_mean' = (1 - momentum)
+    running_mean + momentum mu, running_var' likewise with the unbiased var M / (M - 1).  Returns y, dx, dresidual (with a
+    residual), dweight, dbias, running_mean, running_var, each with `_mag`, `_n`, `_cond`; near_zero [M, C] bool and
+    near_zero_share (see the section comment)."""
+    f64 = lambda t: None if t is None else t.detach().to(torch.float64)   # noqa: E731
+    x64 = f64(x)
+    m, c = x64.shape
+    core = _norm_fp64(x64, (0,), (0,), f64(w).view(1, c), f64(b).view(1, c), f64(residual), eps, relu, f64(dy))
+    res = _norm_result(core, (m, c), (c,), [k for k in _NORM_OUTS if k != "dresidual" or residual is not None])
+    rm, rv = f64(running_mean).view(1, c), f64(running_var).view(1, c)
+    unb = m / max(m - 1, 1)
+
+    def running(mu, s):
+        return (1 - momentum) * rm + momentum * mu, (1 - momentum) * rv + momentum * unb * (s ** -2 - eps)
+
+    new_rm, new_rv = running(core["mean"], core["rstd"])
+    zero = torch.zeros_like(core["mean"])
+    _, j1 = torch.func.jvp(running, (core["mean"], core["rstd"]), (core["d_mean"], zero))
+    _, j2 = torch.func.jvp(running, (core["mean"], core["rstd"]), (zero, core["d_rstd"]))
+    mags = ((1 - momentum) * rm.abs() + momentum * core["mean"].abs(), (1 - momentum) * rv.abs() + momentum * unb * core["var"])
+    for k, v, mag, a, bb in zip(("running_mean", "running_var"), (new_rm, new_rv), mags, j1, j2):
+        res.update({k: v.view(c), k + "_mag": mag.view(c), k + "_n": 1, k + "_cond": (a.abs() + bb.abs()).view(c)})
+    return res
+
+
+def groupnorm_fp64(x, w, b, groups, eps, dy):
+    """GroupNorm of a channels-last x [B, rows, C]: statistics per (sample, group) over rows x C / groups, affine per
+    channel.  Returns y, dx, dweight, dbias with `_mag`, `_n`, `_cond` (dx_n = rows * C / groups, dweight_n = B * rows)."""
+    x64 = x.detach().to(torch.float64)
+    bsz, rows, c = x64.shape
+    cpg = c // groups
+    v = lambda t: t.detach().to(torch.float64).view(1, 1, groups, cpg)   # noqa: E731
+    core = _norm_fp64(x64.view(bsz, rows, groups, cpg), (1, 3), (0, 1), v(w), v(b), None, eps, False,
+                      None if dy is None else dy.detach().to(torch.float64).reshape(bsz, rows, groups, cpg))
+    return _norm_result(core, (bsz, rows, c), (c,), ("y", "dx", "dweight", "dbias"))
+
+
+def add_layernorm_fp64(x, residual, w, b, eps, dy):
+    """LayerNorm(z) over the last axis of z = fp32(x + residual): the fp32 sum is the op's saved tensor and so part of its
+    definition; it is formed in fp32 and everything after it in float64.  Returns y, dx, dresidual (with a residual: the same
+    values as dx), dweight, dbias with `_mag`, `_n`, `_cond` (dx_n = C, dweight_n = rows), and z (float64)."""
+    c = x.shape[-1]
+    z = x.detach().float() if residual is None else x.detach().float() + residual.detach().float()
+    z64 = z.to(torch.float64).reshape(-1, c)
+    v = lambda t: t.detach().to(torch.float64).view(1, c)   # noqa: E731
+    core = _norm_fp64(z64, (1,), (0,), v(w), v(b), None, eps, False,
+                      None if dy is None else dy.detach().to(torch.float64).reshape(-1, c))
+    res = _norm_result(core, tuple(x.shape), (c,), ("y", "dx", "dweight", "dbias"))
+    res["z"] = z64.reshape(x.shape)
+    if residual is not None and dy is not None:
+        for t in ("", "_mag", "_cond", "_n"):
+            res["dresidual" + t] = res["dx" + t]
+    return res

@@ -24,8 +24,11 @@ def test_bn_act(m, c, relu, with_res):
     r = torch.randn(m, c, generator=g).cuda().requires_grad_(True) if with_res else None
     dy = torch.randn(m, c, generator=g).cuda()
     if m == 1:  # nn.BatchNorm1d refuses a single value per channel in training mode; the fused op must agree in spirit
-        with pytest.raises(ValueError):
+        with pytest.raises(ValueError) as want:
             ref_bn(x)
+        with pytest.raises(ValueError) as got:
+            bn_act(x, bn, relu=relu, residual=r)
+        assert str(got.value) == str(want.value)
         return
 
     def run(fn, mod):
