@@ -37,10 +37,9 @@ __device__ __forceinline__ int round16(int x) { return (x + 15) & ~15; }
 // ---- weight packing -----------------------------------------------------------------------
 // packed[((k*R16 + r16)*NP + n)*16 + kk*4 + j] = W(red = r16*16 + 4*j + kk, n) for offset k,
 // where (red, n) = (ci, co) forward, (co, ci) dgrad; zero padded to multiples of 16.
-// for_dgrad bit 1 ("natural order", the 16-byte-gather tile kernel): red = r16*16 + 4*kk + j instead.
 __device__ __forceinline__ void pack_weight_body(const float* __restrict__ w, int cout, int kvol, int cin, int for_dgrad,
                                                  float* __restrict__ packed, unsigned bid, unsigned nblk) {
-  const int natural = for_dgrad & 2, bf3 = for_dgrad & 4;
+  const int bf3 = for_dgrad & 4;
   for_dgrad &= 1;
   const int red = for_dgrad ? cout : cin, nn = for_dgrad ? cin : cout;
   if (bf3) {
@@ -80,7 +79,7 @@ __device__ __forceinline__ void pack_weight_body(const float* __restrict__ w, in
     q /= np;
     const int r16 = (int)(q % r16n);
     const int k = (int)(q / r16n);
-    const int r = natural ? r16 * 16 + 4 * kk + j : r16 * 16 + 4 * j + kk;
+    const int r = r16 * 16 + 4 * j + kk;
     float v = 0.0f;
     if (r < red && n < nn) {
       const int co = for_dgrad ? r : n, ci = for_dgrad ? n : r;
@@ -638,9 +637,8 @@ WgradPlan wgrad_plan(int64_t m_out, int cin, int cout, int kvol) {
   p.nci_blk = (cin + 63) / 64;
   const size_t per = (size_t)kvol * cout * cin * 4;
   // ~2048 workgroups (8 per CU) when the level is large enough (as fast as 4096 with half the partial-block traffic;
-  // 1024 is 15-30 % slower: scripts/tile_sweep.sh), >= 512 rows per chunk, <= 128 MB partials
-  constexpr int64_t fill_env = 2048;
-  const int64_t by_fill = std::max<int64_t>(1, fill_env / ((int64_t)p.nco_blk * p.nci_blk * kvol));
+  // 1024 is 15-30 % slower: profiles/r02_tile_sweep.txt), >= 512 rows per chunk, <= 128 MB partials
+  const int64_t by_fill = std::max<int64_t>(1, 2048 / ((int64_t)p.nco_blk * p.nci_blk * kvol));
   const int64_t by_rows = std::max<int64_t>(1, ceil_div(std::max<int64_t>(m_out, 1), 512));
   const int64_t by_mem = std::max<int64_t>(1, (int64_t)((128ull << 20) / std::max<size_t>(per, 1)));
   int64_t s = std::min(std::min(by_fill, by_rows), by_mem);
@@ -697,10 +695,9 @@ int run_conv(const float* in, int64_t m_in, int cin, const float* wp, const floa
   int nt = 16;
   // With the kernel offsets split over the 4 waves of a workgroup (KS, below) a row tile already is 4 waves, so the
   // 3x3x3 layers fill the chip with fewer tiles: 1400 instead of 2048 lets the 256-channel layers (371 row tiles) take
-  // 4 n-tiles per wave instead of 2 -- half the gathers per MFMA: 205 -> 170 us, 60 -> 72 TFLOP/s (EFG_CONV_FILL).
-  constexpr long long fill_env = 0;
+  // 4 n-tiles per wave instead of 2 -- half the gathers per MFMA: 205 -> 170 us, 60 -> 72 TFLOP/s.
   constexpr int ks_env = 4;
-  const long long fill = fill_env > 0 ? fill_env : ((kvol >= 8 && ks_env > 1) ? 1400 : 2048);
+  const long long fill = (kvol >= 8 && ks_env > 1) ? 1400 : 2048;
   while (nt > 1 && (nt / 2 >= ntiles || row_waves * ((ntiles + nt - 1) / nt) < fill)) nt >>= 1;
   if (nt > ntiles) nt = ntiles >= 16 ? 16 : ntiles >= 8 ? 8 : ntiles >= 4 ? 4 : ntiles >= 2 ? 2 : 1;
   while (nt < ntiles && nt < 16 && (ntiles % nt) != 0) nt <<= 1;  // keep grid.y exact where possible
@@ -726,7 +723,7 @@ using namespace efg;
 
 extern "C" size_t efg_spconv_packed_weight_bytes(int cout, int kvol, int cin, int for_dgrad) {
   if (cout < 1 || cin < 1 || kvol < 1) return 0;
-  for_dgrad &= 1;  // (bit 1 selects the natural channel order, same size)
+  for_dgrad &= 1;  // (bit 2, the bf16x3 layout, is the same size)
   const int red = for_dgrad ? cout : cin, nn = for_dgrad ? cin : cout;
   // + one tile row of slack: kernels with NT > tiles read (zero-weight) past the last n-tile
   return ((size_t)kvol * ((red + 15) / 16) * ((nn + 15) / 16 * 16) * 16 + 16 * 256) * sizeof(float);
@@ -736,9 +733,10 @@ extern "C" int efg_spconv_pack_weight_f32(const float* weight, int cout, int kvo
                                           float* packed, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   EFG_CHECK_ARG(cout >= 1 && cin >= 1 && kvol >= 1, "spconv: bad weight shape");
+  EFG_CHECK_ARG(!(for_dgrad & 2), "spconv: the natural-order weight layout (flag 2, the 16-byte-gather tile kernel) was retired in round 6");
   if (for_dgrad & 4) {   // split-precision layout of the tile kernel's A/B arm: whole 32-channel steps, whole n-tile groups
     const int red = (for_dgrad & 1) ? cout : cin, nn = (for_dgrad & 1) ? cin : cout;
-    EFG_CHECK_ARG(!(for_dgrad & 2) && red % 32 == 0 && nn % 64 == 0,
+    EFG_CHECK_ARG(red % 32 == 0 && nn % 64 == 0,
                   "spconv: the bf16x3 weight layout needs red %% 32 == 0 and n %% 64 == 0 (got %d, %d)", red, nn);
   }
   const size_t bytes = efg_spconv_packed_weight_bytes(cout, kvol, cin, for_dgrad);
@@ -905,8 +903,7 @@ extern "C" int efg_spconv_wgrad_f32(const float* in_feat, int64_t m_in, int cin,
   a.kvol = kvol;
   a.rows_per_split = p.rows_per_split;
   a.nci_blk = p.nci_blk;
-  constexpr bool small_env = true;
-  if (small_env && cin <= 16 && cout <= 32 && m_in == m_out) {
+  if (cin <= 16 && cout <= 32 && m_in == m_out) {
     // low-channel submanifold layers (dense tables: ~15 of 27 offsets per row; the strided stem conv has 4 of 27 and
     // keeps the compacting kernel): one workgroup per (row chunk, group of <= 4 offsets), see conv_wgrad_small_kernel
     const dim3 grid(p.splits, (unsigned)ceil_div(kvol, 4));

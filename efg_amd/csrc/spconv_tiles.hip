@@ -153,7 +153,12 @@ struct TileArgs {
   long long n_tiles;
   int cin, cout, kvol;
   int c16n, np;
-  int pipe, deal, xcd;   // experiment switches (EFG_TILE_PIPE, EFG_TILE_DEAL, EFG_TILE_XCD)
+  // Always R == 2 / 1 / 1.  They stay run-time values: folded into the kernel, the compiler schedules the first weight load of a
+  // step differently and conv_tile_kernel<4, 1, 4, 0> (strided 128 -> 256 forward without stream-K) and conv_small_kernel<1, 2,
+  // false> (whose argument block this is too) run 3 % slower; one alone does not protect them (profiles/spconv_tiles_cleanup_ab.txt)
+  int pipe;   // software-pipelined weight loads
+  int deal;   // the (step, chunk) round-robin over the split-K waves; 0: whole columns (profiles/r02_tile_sweep.txt)
+  int xcd;    // one contiguous range of workgroups per XCD
   // stream-K (MODE & 2)
   const int* sk_prefix;  // [ux + 1] exclusive prefix of the units' item counts (from the plan, for this R)
   float* sk_scratch;     // [grid][R * NT * 256] shares of units that straddle a cut
@@ -176,17 +181,10 @@ struct TileArgs {
   int ny1;
 };
 
-// (The 16-byte-gather variant of rounds 2-5 -- template parameter V4, EFG_TILE_V4=1: natural-order packed weights, XOR-swizzled A
-// tile, one ds_read_b128 per fragment -- measured 3-13 % SLOWER on every res18 layer (profiles/r02_v4_sweep.txt) and was retired
-// in round 6; the template parameter stays 0.)
-#ifndef EFG_TILE_WPE_R2
-#define EFG_TILE_WPE_R2 4   // waves per SIMD asked of the compiler for the stream-K R = 2 shape (A/B builds: scripts/build_ab.sh)
-#endif
-#ifndef EFG_TILE_WPE_R1
-#define EFG_TILE_WPE_R1 5
-#endif
-template <int NT, int R, int KS, int V4, int MODE>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE & 2) ? (R == 2 ? EFG_TILE_WPE_R2 : EFG_TILE_WPE_R1) : 1)))
+// Waves per SIMD asked of the compiler: 4 (R = 2) and 5 (R = 1) for the stream-K shapes, measured in
+// profiles/r04_conv_waves_per_eu_ab.txt -- and what the size of a stream-K launch, hence the cut of its item list, follows.
+template <int NT, int R, int KS, int MODE>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((MODE & 2) ? (R == 2 ? 4 : 5) : 1)))
 conv_tile_kernel(TileArgs a) {
   constexpr int SK = (MODE >> 1) & 1;  // stream-K: the (unit, offset) items are cut into equal shares, one per workgroup
   constexpr int WT = 4 / KS;                         // wave tiles (of R * 16 rows) per workgroup
@@ -383,8 +381,8 @@ conv_tile_kernel(TileArgs a) {
         for (int t = 0; t < NT; ++t) acc[s][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a3, b[t].w, acc[s][t], 0, 0, 0);
       }
     };
-    // software pipeline over the (up to) four 16-channel steps: the weights of step i+1 are in flight during the
-    // MFMAs of step i (they come from L2: ~200+ cycles, a 16-MFMA step is 512)
+    // software pipeline (R = 2) over the four 16-channel steps of a whole chunk: the weights of step i+1 are in flight during
+    // the MFMAs of step i (they come from L2: ~200+ cycles, a 16-MFMA step is 512); R = 1 loses with it (profiles/r02_tile_sweep.txt)
     float4 b0[NT], b1[NT];
     load_b(b0, wbase, boff0, 0);
     if (nc == 4 && a.pipe) {
@@ -405,9 +403,7 @@ conv_tile_kernel(TileArgs a) {
 
   // The (column, channel chunk) steps of the wave tile, in order, are dealt round-robin to its KS waves: every
   // wave gets the same number of steps (+-1) whatever the number of active columns.
-  // deal = 1: the (column, channel chunk) steps of the wave tile, in order, go round-robin to its KS waves (equal
-  // step counts whatever the number of active columns); deal = 0: whole columns go round-robin (a wave reads the
-  // consecutive chunks of the same 16 rows)
+  // (a.deal == 0: whole columns go round-robin instead -- a wave reads the consecutive chunks of the same 16 rows)
   unsigned mycols = cols;
   if (!a.deal && KS > 1) {
     mycols = 0;
@@ -572,17 +568,10 @@ conv_tile_kernel(TileArgs a) {
     // XCD-aware order: consecutive workgroups (neighbouring sorted chunks re-read the same input rows) on one XCD
     unsigned bx = blockIdx.x, by = blockIdx.y;
     const unsigned lin = blockIdx.x + blockIdx.y * gridDim.x, total = gridDim.x * gridDim.y, per = total >> 3;
-    if (a.xcd == 1 && per > 0 && lin < (per << 3)) {          // one contiguous range of workgroups per XCD
+    if (a.xcd == 1 && per > 0 && lin < (per << 3)) {   // one contiguous range of workgroups per XCD
       const unsigned nl = (lin & 7) * per + (lin >> 3);
       bx = nl % gridDim.x;
       by = nl / gridDim.x;
-    } else if (a.xcd == 2 && per > 0 && lin < (per << 3)) {   // ranges of 64 workgroups dealt round-robin to the XCDs
-      const unsigned blk = lin >> 9, in = lin & 511;           // 512 consecutive ids = 8 XCDs x 64
-      const unsigned nl = blk * 512 + (in & 7) * 64 + (in >> 3);
-      if (blk * 512 + 512 <= (per << 3)) {
-        bx = nl % gridDim.x;
-        by = nl / gridDim.x;
-      }
     }
     body(bx, by, 0, 32, 0u, 0u);
     return;
@@ -687,9 +676,6 @@ conv_tile_kernel(TileArgs a) {
 // robin to four accumulators (the tile kernel's four split-K waves; one accumulator below 8 offsets, as there) and added
 // in the same order -- so every golden, tolerance and run-to-run digest downstream is unchanged
 // (tests/test_spconv_gpu.py::test_small_kernel_bits_equal_tile_kernel).
-#ifndef EFG_SMALL_KO
-#define EFG_SMALL_KO 0   // knock-out builds (scripts/build_ab.sh): 1 no weight staging, 2 no row loads, 3 no neighbour loads, 4 no MFMAs, 5 no stores
-#endif
 __device__ __forceinline__ void transpose_pieces(float (&v)[4]) {   // lane group g, element e  <->  lane group e, element g
   // v_permlane32_swap a, b: a's lanes 32..63 <-> b's lanes 0..31; v_permlane16_swap a, b: a's odd 16-lane rows <-> b's even
   // rows (gfx950; scripts/ubench/permlane_probe.hip prints both).  Inline asm with both registers read-write: chained through
@@ -717,7 +703,7 @@ __global__ void __launch_bounds__(kSmallThreads) conv_small_kernel(TileArgs a) {
 #pragma unroll
     for (int q = 0; q < kPieces; ++q) {
       const int f4 = tid + kSmallThreads * q;
-      v[q] = (f4 < total4 && EFG_SMALL_KO != 1) ? src[f4] : make_float4(0.f, 0.f, 0.f, 0.f);
+      v[q] = f4 < total4 ? src[f4] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
     for (int q = 0; q < kPieces; ++q) {
@@ -746,8 +732,7 @@ __global__ void __launch_bounds__(kSmallThreads) conv_small_kernel(TileArgs a) {
       const int ne = a.kvol * 16;
       int ev[(kSmallKmax * 16 + 63) / 64];
 #pragma unroll
-      for (int u = 0; u < (kSmallKmax * 16 + 63) / 64; ++u)
-        ev[u] = EFG_SMALL_KO == 3 ? (int)((tile * 16 + lane + u) % 1000) : src[min(lane + 64 * u, ne - 1)];
+      for (int u = 0; u < (kSmallKmax * 16 + 63) / 64; ++u) ev[u] = src[min(lane + 64 * u, ne - 1)];
       __builtin_amdgcn_wave_barrier();   // (the previous tile's reads of the block are done)
 #pragma unroll
       for (int u = 0; u < (kSmallKmax * 16 + 63) / 64; ++u)
@@ -782,11 +767,6 @@ __global__ void __launch_bounds__(kSmallThreads) conv_small_kernel(TileArgs a) {
         if (gr.col[q] < 0) continue;   // (wave-uniform)
         gr.id[q] = nbs[gr.col[q] * 16 + i];
         const float* rp = a.in + (size_t)max(gr.id[q], 0) * a.cin;
-        if (EFG_SMALL_KO == 2) {
-#pragma unroll
-          for (int e = 0; e < XS; ++e) gr.x[q][e] = (float)gr.id[q];
-          continue;
-        }
         if constexpr (VEC) {
 #pragma unroll
           for (int h = 0; h < C16; ++h) {   // piece kk of the h-th 64-byte half of the row
@@ -805,16 +785,16 @@ __global__ void __launch_bounds__(kSmallThreads) conv_small_kernel(TileArgs a) {
         float4 bw[NT];
 #pragma unroll
         for (int t = 0; t < NT; ++t)
-          bw[t] = EFG_SMALL_KO == 4 ? make_float4(0.f, 0.f, 0.f, 0.f)
-                                    : *reinterpret_cast<const float4*>(wcol + ((h * NT + t) * 16 + i) * 16 + kk * 4);
+          // (through a copy: read straight into bw[t], the 4-byte-load kernels wait for ALL row loads in flight before the next
+          // group's are issued, vmcnt(0) for vmcnt(5): +1 us on the stem's strided forward, profiles/spconv_tiles_cleanup_ab.txt)
+          bw[t] = float4(*reinterpret_cast<const float4*>(wcol + ((h * NT + t) * 16 + i) * 16 + kk * 4));
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
           const float av = x[h * NJ + j];
 #pragma unroll
           for (int t = 0; t < NT; ++t) {
             const float bv = j == 0 ? bw[t].x : j == 1 ? bw[t].y : j == 2 ? bw[t].z : bw[t].w;
-            if (EFG_SMALL_KO == 4) acc[t][0] += av;
-            else acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[t], 0, 0, 0);
           }
         }
       }
@@ -870,7 +850,7 @@ __global__ void __launch_bounds__(kSmallThreads) conv_small_kernel(TileArgs a) {
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         const int co = t * 16 + i;
-        if (row >= 0 && co < a.cout && (EFG_SMALL_KO != 5 || acc[t][r] == 123.456f)) a.out[(long long)row * a.cout + co] = acc[t][r];
+        if (row >= 0 && co < a.cout) a.out[(long long)row * a.cout + co] = acc[t][r];
       }
     }
   }
@@ -886,73 +866,38 @@ int resident_workgroups(K kernel) {
   return per_cu * cus;
 }
 
-template <int NT, int R, int KS, int V4, int MODE>
-void launch_tiles_k(TileArgs a, unsigned gx, unsigned gy, hipStream_t stream) {
+// One launch of conv_tile_kernel<NT, R, KS, MODE> over `ny` n-slices: a grid of (workgroups of 4 / KS wave tiles, n-slices),
+// or -- stream-K (MODE & 2) -- as many workgroups as the device holds at once over the same grid of units.
+template <int NT, int R, int KS, int MODE>
+void launch_tiles(TileArgs a, int ny, hipStream_t stream) {
+  const unsigned gx = (unsigned)ceil_div((a.n_tiles + R - 1) / R, 4 / KS);
   if (MODE & 2) {
-    static const int resident = resident_workgroups(conv_tile_kernel<NT, R, KS, V4, MODE>);
+    static const int resident = resident_workgroups(conv_tile_kernel<NT, R, KS, MODE>);
     a.ux = gx;
-    a.uy = gy;
-    hipLaunchKernelGGL((conv_tile_kernel<NT, R, KS, V4, MODE>), dim3((unsigned)std::min(resident, kStreamKMaxGrid)), dim3(256), 0, stream, a);
+    a.uy = ny;
+    hipLaunchKernelGGL((conv_tile_kernel<NT, R, KS, MODE>), dim3((unsigned)std::min(resident, kStreamKMaxGrid)), dim3(256), 0, stream, a);
   } else {
-    hipLaunchKernelGGL((conv_tile_kernel<NT, R, KS, V4, MODE>), dim3(gx, gy), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((conv_tile_kernel<NT, R, KS, MODE>), dim3(gx, ny), dim3(256), 0, stream, a);
   }
-}
-
-template <int NT, int R, int V4, int MODE>
-void launch_tiles_x(const TileArgs& a, int ny, int ks, hipStream_t stream) {
-  const long long wave_tiles = (a.n_tiles + R - 1) / R;
-  // (stream-K exists for the split-K shape only: one unit per workgroup)
-  if (ks == 4) launch_tiles_k<NT, R, 4, V4, MODE>(a, (unsigned)wave_tiles, ny, stream);
-  else if (ks == 2) launch_tiles_k<NT, R, 2, V4, 0>(a, (unsigned)ceil_div(wave_tiles, 2), ny, stream);
-  else launch_tiles_k<NT, R, 1, V4, 0>(a, (unsigned)ceil_div(wave_tiles, 4), ny, stream);
-}
-
-template <int NT, int R, int V4>
-void launch_tiles_v(const TileArgs& a, int ny, int ks, hipStream_t stream) {
-  // stream-K exists for the 64-channel-wide wave tiles with 4-byte gathers and the split-K shape only (the default shapes)
-  constexpr bool kModes = (NT == 4 && V4 == 0);
-  if (kModes && a.bf3 && ks == 4) {   // the split-precision arm exists for this shape only (run_tiles checked)
-    if (a.sk_scratch) launch_tiles_k<NT, R, 4, V4, kModes ? 6 : 0>(a, (unsigned)((a.n_tiles + R - 1) / R), ny, stream);
-    else launch_tiles_k<NT, R, 4, V4, kModes ? 4 : 0>(a, (unsigned)((a.n_tiles + R - 1) / R), ny, stream);
-    return;
-  }
-  if (kModes && a.sk_scratch && ks == 4) launch_tiles_x<NT, R, V4, kModes ? 2 : 0>(a, ny, ks, stream);
-  else launch_tiles_x<NT, R, V4, 0>(a, ny, ks, stream);
-}
-
-template <int NT, int R>
-void launch_tiles(const TileArgs& a, int ny, int ks, hipStream_t stream) {
-  launch_tiles_v<NT, R, 0>(a, ny, ks, stream);
 }
 
 // The launch shape of a (cin, cout, kvol, rows) convolution: NT n-tiles per wave, R sub-tiles per wave, KS split-K
-// waves, pipelined weight loads.  ONE definition for the launcher below and for efg_spconv_tile_shape (what the host
-// side labels its timings with).
+// waves.  ONE definition for the launcher below and for efg_spconv_tile_shape (what the host side labels its timings with).
 // EFG_TILE_STREAMK: 0 off, 1 (default) where it wins, 2 every eligible shape (tests)
 int streamk_mode() {
   static const int v = getenv("EFG_TILE_STREAMK") ? atoi(getenv("EFG_TILE_STREAMK")) : 1;
   return v;
 }
 
-void tile_shape(int cin, int cout, int kvol, int64_t m_in, int64_t m_out, int* nt_out, int* r_out, int* ks_out, int* pipe_out) {
-  constexpr int r_env = 0;
-  constexpr int ks_env = 0;
-  constexpr int nt_env = 0;
-  constexpr int pipe_env = -1;
+void tile_shape(int cin, int cout, int kvol, int64_t m_in, int64_t m_out, int* nt_out, int* r_out, int* ks_out) {
   const int ntiles = (cout + 15) / 16;
-  int nt = ntiles >= 4 ? 4 : (ntiles >= 2 ? 2 : 1);
-  if (nt_env > 0) nt = nt_env <= 1 ? 1 : (nt_env <= 2 ? 2 : 4);
+  const int nt = ntiles >= 4 ? 4 : (ntiles >= 2 ? 2 : 1);
+  *nt_out = nt;
   // two row sub-tiles per wave (weights loaded once for 32 rows) on the dense tables of the submanifold layers: from
   // 128 reduction channels, and from 64 when the launch is stream-K (the longer units no longer unbalance the launch:
   // 64-channel layer 105 -> 99 us forward, 104 -> 96 us dgrad; without stream-K R = 2 loses there, 107 -> 121 us)
-  int r = (nt >= 4 && kvol >= 8 && m_in == m_out && (cin >= 128 || (streamk_mode() && cin >= 64))) ? 2 : 1;
-  if (r_env > 0) r = r_env >= 2 ? 2 : 1;
-  int ks = (kvol >= 8) ? 4 : 1;
-  if (ks_env > 0) ks = ks_env >= 4 ? 4 : (ks_env >= 2 ? 2 : 1);
-  *nt_out = nt;
-  *r_out = r;
-  *ks_out = ks;
-  *pipe_out = pipe_env >= 0 ? pipe_env : (r == 2 ? 1 : 0);
+  *r_out = (nt >= 4 && kvol >= 8 && m_in == m_out && (cin >= 128 || (streamk_mode() && cin >= 64))) ? 2 : 1;
+  *ks_out = (kvol >= 8) ? 4 : 1;
 }
 
 // Stream-K scratch per (device, stream): kernels of one stream are serialised, so they can share it.  Allocated on first
@@ -987,8 +932,8 @@ int streamk_for_stream(hipStream_t stream, StreamKState** out) {
 // The split-precision arm covers the 64-channel-wide split-K shape (NT = 4, KS = 4) with whole 32-channel reduction steps
 // and whole groups of 4 n-tiles; ONE rule for the launcher, the packer's caller and efg_spconv_tile_bf16x3_ok.
 bool bf16x3_ok(int cin, int cout, int kvol, int64_t m_in, int64_t m_out) {
-  int nt, r, ks, pipe;
-  tile_shape(cin, cout, kvol, m_in, m_out, &nt, &r, &ks, &pipe);
+  int nt, r, ks;
+  tile_shape(cin, cout, kvol, m_in, m_out, &nt, &r, &ks);
   return nt == 4 && ks == 4 && kvol <= 31 && cin >= 64 && cin % 32 == 0 && cout % 64 == 0;
 }
 
@@ -1007,14 +952,14 @@ bool small_shape(int cin, int cout, int kvol, int* c16_out, int* nt_out) {
 }
 
 int run_tiles(const float* in, int64_t m_in, int cin, const float* wp, const float* bias, int cout, int kvol,
-              const void* plan, int64_t m_out, float* out, int flip, int natural_order, int bf3, hipStream_t stream,
+              const void* plan, int64_t m_out, float* out, int flip, int bf3, hipStream_t stream,
               const float* in2 = nullptr, const float* wp2 = nullptr, float* out2 = nullptr) {
   EFG_CHECK_ARG(cin >= 1 && cout >= 1, "spconv tiled: bad channel counts");
   // pairs (TileArgs): wp2 + out2 = two convolutions of one input, wp2 + in2 = one convolution of two inputs
-  EFG_CHECK_ARG(!wp2 || ((in2 != nullptr) != (out2 != nullptr) && !bias && !natural_order && !bf3),
-                "spconv tiled pair: second weights need either a second input or a second output, no bias, the fp32 4-byte path");
+  EFG_CHECK_ARG(!wp2 || ((in2 != nullptr) != (out2 != nullptr) && !bias && !bf3),
+                "spconv tiled pair: second weights need either a second input or a second output, no bias, the fp32 path");
   EFG_CHECK_ARG(wp2 || (!in2 && !out2), "spconv tiled pair: second input / output without second weights");
-  EFG_CHECK_ARG(!bf3 || (!natural_order && bf16x3_ok(cin, cout, kvol, m_in, m_out)),
+  EFG_CHECK_ARG(!bf3 || bf16x3_ok(cin, cout, kvol, m_in, m_out),
                 "spconv tiled: the bf16x3 arm does not cover %d -> %d channels, kvol %d (ask efg_spconv_tile_bf16x3_ok)", cin,
                 cout, kvol);
   EFG_CHECK_ARG(kvol >= 1 && kvol <= 31, "spconv tiled: kernel volume must be in [1,31], got %d", kvol);
@@ -1042,7 +987,6 @@ int run_tiles(const float* in, int64_t m_in, int cin, const float* wp, const flo
   a.wp2 = wp2;
   a.out2 = out2;
   a.ny1 = 0;
-  EFG_CHECK_ARG(!natural_order, "spconv tiled: the natural-order (16-byte gather) variant was retired in round 6 (3-13 %% slower, profiles/r02_v4_sweep.txt)");
   // narrow layers (conv_small_kernel): EFG_CONV_SMALL=0 keeps them on the tile kernel (A/B)
   {
     int c16 = 0, nt_s = 0;
@@ -1072,24 +1016,19 @@ int run_tiles(const float* in, int64_t m_in, int cin, const float* wp, const flo
   // R = 2 sub-tiles per wave (weights loaded once for 32 rows) once the level has enough row tiles to fill the chip
   // that way; n-tiles per wave as many as the grid allows (A reuse); offsets split over the 4 waves of a workgroup
   // (KS) on the small levels, where a wave would otherwise walk ~20 offsets x 4 channel chunks alone.
-  // Launch shape (scripts/tile_sweep.sh, profiles/r02_tile_sweep.txt).  These kernels are latency-bound rather than
-  // MFMA-bound (PMC: matrix pipe 50-60 % busy with 2-4 waves per SIMD), so the shape maximises waves in flight:
+  // Launch shape (profiles/r02_tile_sweep.txt).  These kernels are latency-bound rather than MFMA-bound (PMC: matrix pipe
+  // 50-60 % busy with 2-4 waves per SIMD), so the shape maximises waves in flight:
   //  * KS = 4: the (offset, chunk) steps of a row tile are dealt to the 4 waves of its workgroup (3x3x3 windows);
   //  * R = 2 sub-tiles per wave + software-pipelined weight loads once a step is long enough to amortise the extra
   //    registers (submanifold layers with cin >= 128; the strided layers' sparse tables lose with it), else R = 1;
   //  * NT = min(4, n-tiles): 64 output channels per wave, wider outputs tile over grid.y (each re-gathers A).
-  int nt, r, ks, pipe;
-  tile_shape(cin, cout, kvol, m_in, m_out, &nt, &r, &ks, &pipe);
+  int nt, r, ks;
+  tile_shape(cin, cout, kvol, m_in, m_out, &nt, &r, &ks);
   int ny = (ntiles + nt - 1) / nt;
   if (out2) {   // N pair: the second convolution's n-slices follow the first's in the unit grid
     a.ny1 = ny;
     ny *= 2;
   }
-  constexpr int deal_env = 1;
-  a.pipe = pipe;
-  a.deal = deal_env;
-  constexpr int xcd_env = 1;
-  a.xcd = xcd_env;
   // Stream-K (see the kernel): on by default where it was measured to win -- the 64-channel-wide split-K shape on
   // submanifold tables (every level: -3 % at 64 channels, -5 % at 128, -9 % at 256) and on the strided tables with
   // at least 128 channels on both sides (-11 %); the other strided tables lose with it (short units, many of them).
@@ -1116,18 +1055,31 @@ int run_tiles(const float* in, int64_t m_in, int cin, const float* wp, const flo
     a.sk_epoch = ++st->epoch;   // (under the caller's serialisation of the stream)
     a.sk_fallbacks = st->flags + kStreamKMaxGrid;
   }
-  if (r == 2) {
-    switch (nt) {
-      case 4: launch_tiles<4, 2>(a, ny, ks, stream); break;
-      case 2: launch_tiles<2, 2>(a, ny, ks, stream); break;
-      default: launch_tiles<1, 2>(a, ny, ks, stream); break;
-    }
-  } else {
-    switch (nt) {
-      case 4: launch_tiles<4, 1>(a, ny, ks, stream); break;
-      case 2: launch_tiles<2, 1>(a, ny, ks, stream); break;
-      default: launch_tiles<1, 1>(a, ny, ks, stream); break;
-    }
+  a.pipe = r == 2;
+  a.deal = 1;
+  a.xcd = 1;
+  // Every instantiation that exists, once: MODE bit 1 = stream-K, bit 2 = the bf16x3 arm (both for NT = 4, KS = 4 only).
+  const int mode = (a.sk_scratch ? 2 : 0) | (a.bf3 ? 4 : 0);
+  const int shape = nt * 1000 + r * 100 + ks * 10 + mode;
+  switch (shape) {
+#define EFG_TILE_CASE(NT, R, KS, MODE) \
+  case NT * 1000 + R * 100 + KS * 10 + MODE: launch_tiles<NT, R, KS, MODE>(a, ny, stream); break
+    EFG_TILE_CASE(1, 1, 1, 0);
+    EFG_TILE_CASE(2, 1, 1, 0);
+    EFG_TILE_CASE(4, 1, 1, 0);
+    EFG_TILE_CASE(1, 1, 4, 0);
+    EFG_TILE_CASE(2, 1, 4, 0);
+    EFG_TILE_CASE(4, 1, 4, 0);
+    EFG_TILE_CASE(4, 2, 4, 0);
+    EFG_TILE_CASE(4, 1, 4, 2);
+    EFG_TILE_CASE(4, 2, 4, 2);
+    EFG_TILE_CASE(4, 1, 4, 4);
+    EFG_TILE_CASE(4, 2, 4, 4);
+    EFG_TILE_CASE(4, 1, 4, 6);
+    EFG_TILE_CASE(4, 2, 4, 6);
+#undef EFG_TILE_CASE
+    default:
+      EFG_CHECK_ARG(false, "spconv tiled: no conv_tile_kernel<%d, %d, %d, %d> (tile_shape and the launcher disagree)", nt, r, ks, mode);
   }
   EFG_LAUNCH_CHECK();
   return EFG_OK;
@@ -1159,16 +1111,16 @@ extern "C" int efg_spconv_tile_plan(const int32_t* nbr, int64_t m, int kvol, voi
 
 extern "C" int efg_spconv_tile_shape(int cin, int cout, int kvol, int64_t m_in, int64_t m_out, int* nt, int* r, int* ks) {
   EFG_CHECK_ARG(cin >= 1 && cout >= 1 && kvol >= 1 && nt && r && ks, "tile_shape: bad arguments");
-  int pipe = 0;
-  tile_shape(cin, cout, kvol, m_in, m_out, nt, r, ks, &pipe);
+  tile_shape(cin, cout, kvol, m_in, m_out, nt, r, ks);
   return EFG_OK;
 }
 
 extern "C" int efg_spconv_forward_tiled_f32(const float* in_feat, int64_t m_in, int cin, const float* packed_weight,
                                             const float* bias, int cout, int kvol, const void* plan, int64_t m_out,
                                             int flip_offsets, float* out_feat, void* stream) {
-  return run_tiles(in_feat, m_in, cin, packed_weight, bias, cout, kvol, plan, m_out, out_feat, flip_offsets & 1, (flip_offsets >> 1) & 1,
-                   (flip_offsets >> 2) & 1, (hipStream_t)stream);
+  EFG_CHECK_ARG(!(flip_offsets & 2), "spconv tiled: the natural-order (16-byte gather) variant was retired in round 6 (3-13 %% slower, profiles/r02_v4_sweep.txt)");
+  return run_tiles(in_feat, m_in, cin, packed_weight, bias, cout, kvol, plan, m_out, out_feat, flip_offsets & 1, (flip_offsets >> 2) & 1,
+                   (hipStream_t)stream);
 }
 
 extern "C" int efg_spconv_tiled_pair_f32(const float* in_a, const float* in_b, int64_t m_in, int cin, const float* packed_a,
@@ -1176,7 +1128,7 @@ extern "C" int efg_spconv_tiled_pair_f32(const float* in_a, const float* in_b, i
                                          int flip_offsets, float* out_a, float* out_b, void* stream) {
   EFG_CHECK_ARG(packed_a && packed_b && in_a && out_a, "spconv tiled pair: null pointer");
   EFG_CHECK_ARG((flip_offsets & ~1) == 0, "spconv tiled pair: only the offset-flip flag is accepted");
-  return run_tiles(in_a, m_in, cin, packed_a, nullptr, cout, kvol, plan, m_out, out_a, flip_offsets & 1, 0, 0, (hipStream_t)stream,
+  return run_tiles(in_a, m_in, cin, packed_a, nullptr, cout, kvol, plan, m_out, out_a, flip_offsets & 1, 0, (hipStream_t)stream,
                    in_b, packed_b, out_b);
 }
 

@@ -76,8 +76,7 @@ constexpr int kMaxSlots = 2048;
 inline int sched_slots(long long n_tiles, int kvol, int nblk, int resident) {
   // ~0.55 of the (tile, offset) pairs of a submanifold window are active, fewer on strided tables: an estimate is enough,
   // it only sets the slot size
-  constexpr int units_env = kUnitsPerSlot;
-  const double want = (double)n_tiles * kvol * 0.55 / units_env * nblk;          // workgroups
+  const double want = (double)n_tiles * kvol * 0.55 / kUnitsPerSlot * nblk;      // workgroups
   const long long fills = std::max<long long>(1, (long long)(want / resident + 0.5));
   long long slots = fills * resident / nblk;
   slots = std::max<long long>(slots, kvol);
@@ -204,8 +203,7 @@ __global__ void __launch_bounds__(256) wgt_schedule_kernel(const unsigned* __res
 // slots are sorted by their first tile (all offsets together) and dealt in eighths: XCD x walks the x-th eighth of the
 // rows in tile order with the offsets of a range next to each other in time (workgroup 8 q + x = q-th slot of the x-th
 // eighth).  One workgroup, an LDS bitonic sort of <= 2048 keys.
-__global__ void __launch_bounds__(1024) wgt_order_kernel(const int4* __restrict__ entry, int slots, int4* __restrict__ dispatch,
-                                                          int by_position) {
+__global__ void __launch_bounds__(1024) wgt_order_kernel(const int4* __restrict__ entry, int slots, int4* __restrict__ dispatch) {
   __shared__ unsigned long long key[kMaxSlots];
   const int tid = threadIdx.x;
   int n2 = 1;
@@ -237,10 +235,7 @@ __global__ void __launch_bounds__(1024) wgt_order_kernel(const int4* __restrict_
   const int d_n = sched_dispatch_dev(slots), per = d_n >> 3;
   for (int d = tid; d < d_n; d += 1024) dispatch[d] = make_int4(-1, 0, 0, 0);
   __syncthreads();
-  for (int s = tid; s < slots; s += 1024) {
-    if (by_position) dispatch[8 * (s % per) + s / per] = entry[(int)(key[s] & 0xffffu)];
-    else dispatch[s] = entry[s];   // (A/B: table order)
-  }
+  for (int s = tid; s < slots; s += 1024) dispatch[8 * (s % per) + s / per] = entry[(int)(key[s] & 0xffffu)];
 }
 
 template <int NCO, int NCI>
@@ -514,8 +509,8 @@ extern "C" int efg_spconv_wgrad_sched(const void* plan, int64_t m_out, int cin, 
   int* kfirst = reinterpret_cast<int*>(dispatch + sched_dispatch(slots));
   int4* entry = reinterpret_cast<int4*>(kfirst + 36);
   hipLaunchKernelGGL(wgt_schedule_kernel, dim3(kvol), dim3(256), 0, stream, pv.vm, pv.n_tiles, kvol, slots, entry, kfirst);
-  constexpr int order_env = 1;   // (0: table order -- the losing A/B arm of round 3, profiles/r03_wgrad_dispatch_order_ab.txt)
-  hipLaunchKernelGGL(wgt_order_kernel, dim3(1), dim3(1024), 0, stream, entry, slots, dispatch, order_env);
+  // (dispatched in table order instead: the losing A/B arm of round 3, profiles/r03_wgrad_dispatch_order_ab.txt)
+  hipLaunchKernelGGL(wgt_order_kernel, dim3(1), dim3(1024), 0, stream, entry, slots, dispatch);
   EFG_LAUNCH_CHECK();
   return EFG_OK;
 }

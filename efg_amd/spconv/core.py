@@ -72,13 +72,6 @@ def _build_rnbr(nbr, m_out, kvol, m_in):
     return (r[:, :m_in] if m_in > 0 else r[:, :0]).contiguous()
 
 
-def _tiled():
-    """Mask-sorted row tiles (csrc/spconv_tiles.hip) for forward / dgrad of every window of at most 31 offsets; the
-    generation-one kernels (csrc/spconv_conv.hip) remain for larger windows only (the EFG_CONV_TILED=0 switch of rounds 2-5 was
-    retired in round 6: profiles/r02_gen1_vs_tiled_per_layer.txt)."""
-    return True
-
-
 _SHAPE_CACHE = {}
 
 
@@ -221,8 +214,8 @@ _PACK_REGISTRY = {}
 
 
 def _packed_weight(w, flags, owner=None):
-    """MFMA-order copy of w [cout, kvol, cin] for `flags` (bit 0: data-gradient layout, bit 1: natural channel order,
-    bit 2: split-precision arm), cached on `owner` (the layer's Parameter) when given."""
+    """MFMA-order copy of w [cout, kvol, cin] for `flags` (bit 0: data-gradient layout, 4: the split-precision arm's layout),
+    cached on `owner` (the layer's Parameter) when given."""
     lib = L.lib()
     cout, kvol, cin = w.shape
     cached = owner is not None and _PACK_CACHE_ON and w.is_cuda
@@ -254,15 +247,17 @@ def _conv_forward(features, w, bias, rb, owner=None):
     """features [m_in,cin], w [cout,kvol,cin] -> [m_out,cout]"""
     lib = L.lib()
     cout, kvol, cin = w.shape
-    tiled = _tiled() and kvol <= 31 and rb.m_out > 0
-    nat = _arm_bf16x3(cin, cout, kvol, rb.m_in, rb.m_out) if tiled else 0   # (bit 2 of the flag word: the split-precision arm)
-    packed = _packed_weight(w, 0 | nat, owner)
+    # mask-sorted row tiles (csrc/spconv_tiles.hip) for every window of at most 31 offsets; the generation-one kernels
+    # (csrc/spconv_conv.hip) remain for larger windows and empty tables (profiles/r02_gen1_vs_tiled_per_layer.txt)
+    tiled = kvol <= 31 and rb.m_out > 0
+    arm = _arm_bf16x3(cin, cout, kvol, rb.m_in, rb.m_out) if tiled else 0   # (4 in the flag word: the split-precision arm)
+    packed = _packed_weight(w, 0 | arm, owner)
     out = torch.empty((rb.m_out, cout), dtype=torch.float32, device=features.device)
     if tiled:
         plan = rb.plan_fwd()
         with _prof.timed(_tile_kernel_name(cin, cout, kvol, rb.m_in, rb.m_out), _Cost(rb, cin, cout, "fwd")):
             L.check(lib.efg_spconv_forward_tiled_f32(L.ptr(features), rb.m_in, cin, L.ptr(packed), L.ptr(bias), cout,
-                                                     kvol, L.ptr(plan), rb.m_out, 0 | nat, L.ptr(out), L.stream()))
+                                                     kvol, L.ptr(plan), rb.m_out, 0 | arm, L.ptr(out), L.stream()))
         return out
     with _prof.timed(_fwd_kernel_name(cout, rb.m_out, kvol), _Cost(rb, cin, cout, "fwd")):
         L.check(lib.efg_spconv_forward_f32(L.ptr(features), rb.m_in, cin, L.ptr(packed), L.ptr(bias), cout, kvol,
@@ -273,15 +268,15 @@ def _conv_forward(features, w, bias, rb, owner=None):
 def _conv_dgrad(grad_out, w, rb, owner=None):
     lib = L.lib()
     cout, kvol, cin = w.shape
-    tiled = _tiled() and kvol <= 31 and rb.m_in > 0
-    nat = _arm_bf16x3(cout, cin, kvol, rb.m_out, rb.m_in) if tiled else 0
-    packed = _packed_weight(w, 1 | nat, owner)
+    tiled = kvol <= 31 and rb.m_in > 0
+    arm = _arm_bf16x3(cout, cin, kvol, rb.m_out, rb.m_in) if tiled else 0
+    packed = _packed_weight(w, 1 | arm, owner)
     grad_in = torch.empty((rb.m_in, cin), dtype=torch.float32, device=grad_out.device)
     if tiled:
         plan, flip = rb.plan_dgrad()
         with _prof.timed(_tile_kernel_name(cout, cin, kvol, rb.m_out, rb.m_in), _Cost(rb, cin, cout, "dgrad")):
             L.check(lib.efg_spconv_forward_tiled_f32(L.ptr(grad_out), rb.m_out, cout, L.ptr(packed), None, cin, kvol,
-                                                     L.ptr(plan), rb.m_in, flip | nat, L.ptr(grad_in), L.stream()))
+                                                     L.ptr(plan), rb.m_in, flip | arm, L.ptr(grad_in), L.stream()))
         return grad_in
     rnbr = rb.rnbr
     order = rb.dgrad_order()
@@ -315,7 +310,7 @@ def _conv_wgrad(features, grad_out, rb):
 def _pair_ok(rb, w_a, w_b, cin, cout):
     """Can the two convolutions (weights [cout, kvol, cin] each) over `rb` run as the pair launches of csrc/spconv_tiles.hip /
     spconv_wgt.hip?  (the tiled fp32 path with the default weight order; EFG_CONV_PAIR=0: two launches each, A/B)"""
-    return (os.environ.get("EFG_CONV_PAIR", "1") != "0" and _tiled() and rb.kvol <= 31 and rb.m_out > 0 and rb.m_in > 0
+    return (os.environ.get("EFG_CONV_PAIR", "1") != "0" and rb.kvol <= 31 and rb.m_out > 0 and rb.m_in > 0
             and w_a.shape == w_b.shape
             and not _arm_bf16x3(cin, cout, rb.kvol, rb.m_in, rb.m_out) and not _arm_bf16x3(cout, cin, rb.kvol, rb.m_out, rb.m_in))
 

@@ -166,9 +166,8 @@ int efg_spconv_build_rnbr(const int32_t* nbr, int64_t m_out, int kvol, int64_t m
  * are re-packed once per call site into MFMA B-operand order (one 16-byte load per lane feeds four
  * v_mfma_f32_16x16x4_f32):  for_dgrad = 0: packed[k][cin/16][cout_pad][16]  (reduce over cin)
  *                           for_dgrad = 1: packed[k][cout/16][cin_pad][16]  (reduce over cout).
- * Within a 16-channel group the lane kk's fragment holds channels {kk, kk+4, kk+8, kk+12}; for_dgrad | 2 ("natural
- * order": {4kk .. 4kk+3}) is the layout of the 16-byte-gather tile kernel that was retired in round 6 -- the packer still
- * writes it, no convolution entry point takes it.
+ * Within a 16-channel group the lane kk's fragment holds channels {kk, kk+4, kk+8, kk+12}.  for_dgrad | 2 (the "natural
+ * order" {4kk .. 4kk+3} of the 16-byte-gather tile kernel that was retired in round 6) is refused.
  * for_dgrad | 4: the split-precision (bf16 x 3) layout of the tile kernel's A/B arm (flip_offsets | 4 there; reduction
  * width a multiple of 32, output width a multiple of 64; same size): per (offset, 32-channel step, n-tile of 16) the 64
  * lanes' 8 bf16 of W_hi, then of W_lo.  efg_spconv_tile_bf16x3_ok says whether a layer is covered. */
@@ -213,7 +212,8 @@ int efg_spconv_tile_plan(const int32_t* nbr, int64_t m, int kvol, void* plan, si
  * autograd threads never overlap on a stream). */
 /* The launch shape efg_spconv_forward_tiled_f32 uses for these sizes: n-tiles (of 16 output channels) per wave, row
  * sub-tiles per wave, split-K waves -- i.e. the conv_tile_kernel<NT, R, KS> instantiation; the host labels its timings
- * with it (one definition shared with the launcher, so labels cannot drift from what ran). */
+ * with it (one definition shared with the launcher, so labels cannot drift from what ran; a shape that has no instantiation
+ * is an error of the launch, never another instantiation). */
 int efg_spconv_tile_shape(int cin, int cout, int kvol, int64_t m_in, int64_t m_out, int* nt, int* r, int* ks);
 int efg_spconv_forward_tiled_f32(const float* in_feat, int64_t m_in, int cin, const float* packed_weight,
                                  const float* bias, int cout, int kvol, const void* plan, int64_t m_out,

@@ -1,5 +1,6 @@
 #!/bin/bash
-# A/B build of ONE translation unit: scripts/build_ab.sh spconv_tiles.hip libefg_hip_ab.so -DEFG_TILE_EARLYB=0
+# A/B build of ONE translation unit with extra compiler flags: scripts/build_ab.sh spconv_tiles.hip libefg_hip_ab.so -O2
+# (or an edited copy of the source under another name in efg_amd/csrc/);
 # links the alternate object with the other objects of efg_amd/lib/ (build the main library first); run a leg with
 # EFG_HIP_LIB_AB=libefg_hip_ab.so.  The alternate .so is git-ignored and travels to the GPU box like the main one.
 set -e
