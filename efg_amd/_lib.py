@@ -47,10 +47,6 @@ _SIGS = {
     "efg_spconv_packed_weight_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "efg_spconv_pack_weight_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "efg_spconv_pack_weights_multi": (c_int, [c_void_p, c_int, c_void_p]),
-    "efg_spconv_forward_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64,
-                                       c_void_p, c_void_p]),
-    "efg_spconv_dgrad_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p,
-                                     c_void_p, c_void_p]),
     "efg_spconv_tile_plan_bytes": (c_size_t, [c_int64, c_int]),
     "efg_spconv_tile_plan": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p]),
     "efg_spconv_forward_tiled_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
@@ -61,7 +57,6 @@ _SIGS = {
     "efg_spconv_tile_bf16x3_ok": (c_int, [c_int, c_int, c_int, c_int64, c_int64]),
     "efg_spconv_streamk_fallbacks": (c_int, [c_void_p, c_int]),
     "efg_ticket_ring_errors": (c_int, [c_void_p, c_int]),
-    "efg_spconv_parity_order": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "efg_spconv_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
     "efg_spconv_wgrad_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
                                      c_void_p, c_size_t, c_void_p]),

@@ -23,7 +23,7 @@ def active():
 
 
 class timed:
-    """with timed("conv_fwd_kernel<4>", lambda: (bytes, flops)): <single kernel launch>"""
+    """with timed("conv_tile_kernel<4>",lambda: (bytes, flops)): <single kernel launch>"""
 
     def __init__(self, name, cost):
         self.name, self.cost = name, cost

@@ -12,6 +12,9 @@
 namespace efg {
 
 constexpr int kWave = 64;
+// Most kernel offsets a sparse-convolution window may have (host-side checks of spconv_conv / _tiles / _wgt.hip): a tile
+// plan keeps a tile's active offsets in ONE 32-bit word next to its 31 per-offset masks (tile_plan.h).
+constexpr int kSpconvMaxKvol = 31;
 
 void set_error(const char* fmt, ...);
 

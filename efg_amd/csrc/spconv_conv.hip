@@ -1,24 +1,16 @@
-// Sparse convolution arithmetic for gfx950: output-stationary gathered implicit GEMM on
-// v_mfma_f32_16x16x4_f32 (exact fp32, the dtype the reference trains in), forward / dgrad / wgrad.
+// Sparse convolution for gfx950, the two parts that work from the weights and the neighbour table alone (exact fp32 on
+// v_mfma_f32_16x16x4_f32, the dtype the reference trains in; reference: spconv's gather -> GEMM -> scatter-add per kernel
+// offset as exercised by efg/modeling/backbones/sparse_net.py:79-98,120-165,273-309,485-545, contract SURVEY.md B.6).
 //
-// Replaces spconv's gather -> GEMM -> scatter-add per kernel offset as exercised by
-// efg/modeling/backbones/sparse_net.py:79-98,120-165,273-309,485-545 (contract SURVEY.md B.6).
-// No scatter and no atomics: with nbr[k][o] (spconv_index.hip) every output row is produced once,
-//     out[o][:] = sum_k  in[nbr[k][o]][:] . W[:,k,:]^T
-// and dgrad is the SAME kernel driven by the transposed table rnbr and transposed weights.
+// Weight packer: the [cout][kvol][cin] parameter re-ordered into the MFMA B-operand order the tile kernels of
+// spconv_tiles.hip load (one 16-byte load per lane feeds four MFMAs), for the forward product and for the data gradient
+// (reduction over cout), in fp32 or as the hi / lo bf16 pieces of the split-precision arm; one layer per launch, or every
+// layer of a model in one.
 //
-// forward / dgrad kernel, per wave (waves are independent; a 256-thread block is 4 of them):
-//   * 16 output rows x all output channels: NT accumulator tiles of 16x16 (4 VGPRs each);
-//   * the wave's nbr column block (kvol x 16 ints) is staged in LDS once; offsets k for which none
-//     of the 16 rows has a neighbour are skipped entirely (rows are in spatial order, so validity is
-//     spatially coherent);
-//   * for an active k the 16 gathered input rows are read as contiguous 256-byte runs (one row per
-//     load instruction, 16 loads in flight), staged in a wave-private LDS tile with row stride
-//     CK+2 (bank-conflict-free ds_read_b32 of the A fragment), double-buffered against the MFMAs;
-//   * the B fragments come straight from L1/L2 as 16-byte loads of weights pre-packed into MFMA
-//     operand order (efg_spconv_pack_weight_f32): one load feeds four MFMAs.
-// wgrad: per (row chunk, 64x64 block of dW, kernel offset) workgroup; valid pairs compacted into dense
-// 64-pair tiles, G^T x gathered-X on the same MFMA, partials to a workspace, deterministic reduce.
+// Table-walking weight gradient, dW[co][k][ci] = sum_o G[o][co] * X[nbr[k][o]][ci] from nbr[k][o] (spconv_index.hip)
+// itself: per (row chunk, 64x64 block of dW, kernel offset) workgroup the valid pairs are compacted into dense 32-pair
+// tiles, G^T x gathered-X on the MFMA, partials to a workspace, deterministic reduce.  It takes any channel widths: the
+// layers the plan-walking weight gradient (spconv_wgt.hip) does not cover run here, and that kernel is tested against it.
 #include "common.h"
 
 #include <cstdlib>
@@ -27,10 +19,6 @@ namespace efg {
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kCK = 64;           // channels per staged chunk
-constexpr int kAStride = kCK + 2;  // 2 x odd -> conflict-free A-fragment reads
-constexpr int kMaxKvol = 64;
 
 __device__ __forceinline__ int round16(int x) { return (x + 15) & ~15; }
 
@@ -65,7 +53,8 @@ __device__ __forceinline__ void pack_weight_body(const float* __restrict__ w, in
   }
   const int r16n = round16(red) / 16, np = round16(nn);
   const long long total = (long long)kvol * r16n * np * 16;
-  // (+ the slack row kernels with NT > tiles read past the last n-tile: written as zeros here, no separate memset)
+  // (+ the slack row conv_tile_kernel reads past the last n-tile when its NT does not divide the tiles -- 48 output channels are
+  // 3 n-tiles, and the second NT = 2 slice loads a fourth: written as zeros here, no separate memset)
   for (long long e = (long long)bid * blockDim.x + threadIdx.x; e < total + 16 * 256;
        e += (long long)nblk * blockDim.x) {
     if (e >= total) {
@@ -104,226 +93,6 @@ struct PackItem {
 __global__ void __launch_bounds__(256) pack_weights_multi_kernel(const PackItem* __restrict__ items) {
   const PackItem it = items[blockIdx.y];
   pack_weight_body(it.w, it.cout, it.kvol, it.cin, it.flags, it.packed, blockIdx.x, gridDim.x);
-}
-
-// ---- forward / dgrad ------------------------------------------------------------------------
-struct ConvArgs {
-  const float* in;     // [m_in][cin]
-  const float* wp;     // packed
-  const float* bias;   // [cout] or null
-  const int* nbr;      // [kvol][m_out]
-  float* out;          // [m_out][cout]
-  const int* order;    // null, or a permutation of the m_out rows: tile t computes rows order[16 t .. 16 t + 15]
-  long long m_out;
-  int cin, cout, kvol;
-  int c16n;            // round16(cin)/16
-  int np;              // round16(cout)
-};
-
-// KS: the kernel offsets of a 16-row tile are split over KS waves of the workgroup (split-K).  A wave walks its
-// offsets one after the other -- gather, stash, MFMA -- so its run time is a serial chain of gather latencies, and a
-// level only has a few waves per SIMD to overlap them (PMC: 34 % MFMA busy, 45 % of wave cycles waiting).  Splitting
-// the offsets multiplies the waves and divides the chain; the partial accumulators meet in LDS.
-template <int NT, int KV = 32, int KS = 1>
-__global__ void __launch_bounds__(256) conv_fwd_kernel(ConvArgs a) {
-  // wave-private staging: ONE A tile per wave (the wave itself orders compute -> refill; the prefetch
-  // lives in registers) and the wave's rulebook block; 21 KB per workgroup for KV = 32
-  __shared__ float a_tile[4][16 * kAStride];
-  __shared__ int nbr_tile[4 / KS][KV * 16];  // one rulebook block per row tile (shared by its KS waves)
-  __shared__ unsigned vmask_tile[4 / KS][KV];  // per offset: which of the 16 tile rows have a neighbour
-  __shared__ int prow_tile[4 / KS][16];        // the tile's rows when a row order is given (else r0 + j)
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  constexpr int TILES = 4 / KS;          // row tiles per workgroup
-  const int tile = wv / KS, part = wv % KS;
-  // XCD-aware block order.  Workgroups are dealt round-robin to the 8 XCDs (each with its own L2) by linear id;
-  // rows are in canonical spatial order, so the 27 gathers of a row block hit rows that neighbouring row blocks
-  // also read.  With the hardware order those neighbours sit on 8 different L2s (measured: 8x the algorithmic
-  // bytes fetched past L2); renumbering gives every XCD one contiguous range of row blocks.
-  unsigned bx = blockIdx.x, by = blockIdx.y;
-  {
-    const unsigned lin = blockIdx.x + blockIdx.y * gridDim.x, total = gridDim.x * gridDim.y, per = total >> 3;
-    if (per > 0 && lin < (per << 3)) {
-      const unsigned nl = (lin & 7) * per + (lin >> 3);
-      bx = nl % gridDim.x;
-      by = nl / gridDim.x;
-    }
-  }
-  const long long r0 = ((long long)bx * TILES + tile) * 16;
-  const bool tile_ok = r0 < a.m_out;
-  if (KS == 1 && !tile_ok) return;  // whole wave out of range (with KS == 1 waves never sync with each other)
-  float* at0 = a_tile[wv];
-  int* nb = nbr_tile[wv / KS];
-  unsigned* vm = vmask_tile[wv / KS];
-  const int n_tile0 = by * NT;  // first n-tile of this block
-
-  // stage the wave's rulebook block and find the active offsets
-  int* prow = prow_tile[wv / KS];
-  if (a.order) {  // (uniform) rows of this tile through the caller's order: e.g. grouped by coordinate parity, so that
-                  // the rows of a tile of a strided layer's dgrad need the same few offsets
-    if (part == 0 && lane < 16) prow[lane] = (r0 + lane < a.m_out) ? a.order[r0 + lane] : -1;
-    if (KS > 1) __syncthreads(); else __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    for (int e = lane + 64 * part; e < a.kvol * 16; e += 64 * KS) {
-      const int k = e >> 4, j = e & 15;
-      const int pr = prow[j];
-      nb[e] = (pr >= 0) ? a.nbr[(long long)k * a.m_out + pr] : -1;
-    }
-  } else {
-    for (int e = lane + 64 * part; e < a.kvol * 16; e += 64 * KS) {
-      const int k = e >> 4, j = e & 15;
-      nb[e] = (r0 + j < a.m_out) ? a.nbr[(long long)k * a.m_out + r0 + j] : -1;
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (KS > 1) __syncthreads();  // the tile's waves each staged a share of the block
-  unsigned long long active = 0;
-  {
-    int seen = 0;
-    for (int k = 0; k < a.kvol; ++k) {
-      const int v = (lane < 16) ? nb[k * 16 + lane] : -1;
-      const unsigned long long bal = __ballot(v >= 0);
-      if (lane == 0) vm[k] = (unsigned)bal;  // the tile's waves all write the same word
-      if (bal) {
-        if (seen % KS == part) active |= 1ull << k;  // this wave's share of the tile's active offsets
-        ++seen;
-      }
-    }
-    if (!tile_ok) active = 0;
-  }
-  // The gathers only need byte offsets: turn the row numbers into offsets once (invalid -> row 0, a legal address;
-  // its value is dropped through the scalar mask), so a gather costs one add + one select per row on the VALU.
-  if (KS > 1) __syncthreads(); else __builtin_amdgcn_wave_barrier();
-  for (int e = lane + 64 * part; e < a.kvol * 16; e += 64 * KS) nb[e] = (int)((unsigned)max(nb[e], 0) * (unsigned)a.cin * 4u);
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  if (KS > 1) __syncthreads();
-
-  f32x4 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    float b = 0.0f;
-    const int co = (n_tile0 + t) * 16 + (lane & 15);
-    if (a.bias && co < a.cout && part == 0) b = a.bias[co];
-    acc[t] = f32x4{b, b, b, b};
-  }
-
-  const int nchunk = (a.c16n * 16 + kCK - 1) / kCK;  // channel chunks of 64 per offset
-  float pre[16];
-  unsigned pre_mask = 0;
-
-  // gather of (k, chunk) into registers: row j of the wave -> pre[j] (lane = channel)
-  auto gather = [&](int k, int ch) {
-    // Branch-free: a predicated load compiles to a branch + its own basic block, and the waitcnt pass then
-    // serialises the 16 loads (one s_waitcnt vmcnt(0) per load).  Clamp the address, load always, select.
-    // lanes past cin read a clamped (finite) channel: the packed weights are zero there, so nothing is selected
-    // per lane; rows without a neighbour are dropped with the scalar mask of the offset
-    const unsigned cc4 = (unsigned)min(ch * kCK + lane, a.cin - 1) * 4u;
-    const unsigned vmk = (unsigned)__builtin_amdgcn_readfirstlane((int)vm[k]);
-    unsigned offs[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) offs[j] = (unsigned)nb[k * 16 + j] + cc4;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) pre[j] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.in) + offs[j]);
-    pre_mask = vmk;  // rows without a neighbour are zeroed at stash time (a select here would wait for the loads)
-  };
-  auto stash = [&](float* at) {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) at[j * kAStride + lane] = ((pre_mask >> j) & 1u) ? pre[j] : 0.0f;
-  };
-  auto compute = [&](const float* at, int k, int ch) {
-    const int c16_lo = ch * (kCK / 16);
-    const int c16_hi = min(c16_lo + kCK / 16, a.c16n);
-    const int m = lane & 15, kk = lane >> 4;
-    for (int c16 = c16_lo; c16 < c16_hi; ++c16) {
-      const float* ap = at + m * kAStride + (c16 - c16_lo) * 16 + kk;
-      const float a0 = ap[0], a1 = ap[4], a2 = ap[8], a3 = ap[12];
-      // 32-bit byte offset into the packed weights (a few MB): saddr + voffset loads
-      const unsigned boff = ((((unsigned)k * (unsigned)a.c16n + (unsigned)c16) * (unsigned)a.np + (unsigned)(n_tile0 * 16 + m)) * 16u +
-                             (unsigned)(kk * 4)) * 4u;
-      float4 b[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t)
-        b[t] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(a.wp) + boff + (unsigned)t * 1024u);
-      // k-step outer, n-tile inner: consecutive MFMAs hit different accumulators (a 16x16x4 f32 MFMA
-      // issues every 32 cycles but its result is ready after 40)
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b[t].x, acc[t], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b[t].y, acc[t], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, b[t].z, acc[t], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a3, b[t].w, acc[t], 0, 0, 0);
-    }
-  };
-
-  // software pipeline over the (active offset, chunk) steps
-  const int nsteps = __popcll(active) * nchunk;
-  if (nsteps > 0) {
-    unsigned long long rem = active;
-    int k_cur = __ffsll((long long)rem) - 1, ch_cur = 0;
-    gather(k_cur, ch_cur);
-    stash(at0);
-    for (int s = 0; s < nsteps; ++s) {
-      // next step coordinates
-      int k_nxt = k_cur, ch_nxt = ch_cur + 1;
-      if (ch_nxt == nchunk) {
-        ch_nxt = 0;
-        rem &= rem - 1;
-        k_nxt = rem ? __ffsll((long long)rem) - 1 : -1;
-      }
-      const bool more = (s + 1 < nsteps);
-      if (more) gather(k_nxt, ch_nxt);  // global loads in flight during the MFMAs below
-      __builtin_amdgcn_wave_barrier();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      compute(at0, k_cur, ch_cur);
-      __builtin_amdgcn_wave_barrier();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // all fragment reads done before the refill
-      if (more) stash(at0);
-      k_cur = k_nxt;
-      ch_cur = ch_nxt;
-    }
-  }
-
-  if (KS > 1) {
-    // partial accumulators of the tile's other waves: through the (now idle) A tiles, 16 x 16 floats per n-tile
-    __syncthreads();  // every wave is done with its A tile
-    float* red = a_tile[wv];
-    for (int t0 = 0; t0 < NT; t0 += 4) {  // 4 n-tiles (1024 floats) fit one A tile (16 x 66 floats)
-      if (part != 0) {
-#pragma unroll
-        for (int t = t0; t < NT && t < t0 + 4; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) red[((t - t0) * 4 + r) * 64 + lane] = acc[t][r];
-      }
-      __syncthreads();
-      if (part == 0) {
-        for (int p = 1; p < KS; ++p) {
-          const float* o = a_tile[wv + p];
-#pragma unroll
-          for (int t = t0; t < NT && t < t0 + 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[t][r] += o[((t - t0) * 4 + r) * 64 + lane];
-        }
-      }
-      __syncthreads();
-    }
-    if (part != 0 || !tile_ok) return;
-  }
-  // C/D layout of 16x16x4: col = lane & 15, row = (lane >> 4) * 4 + reg
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int co = (n_tile0 + t) * 16 + (lane & 15);
-    if (co < a.cout) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int j = (lane >> 4) * 4 + r;
-        const long long row = a.order ? (long long)prow[j] : ((r0 + j < a.m_out) ? r0 + j : -1);
-        if (row >= 0) a.out[row * a.cout + co] = acc[t][r];
-      }
-    }
-  }
 }
 
 // ---- wgrad ------------------------------------------------------------------------------------
@@ -652,70 +421,6 @@ WgradPlan wgrad_plan(int64_t m_out, int cin, int cout, int kvol) {
   return p;
 }
 
-template <int NT>
-void launch_fwd(const ConvArgs& a, int nblk_y, int ks, hipStream_t stream) {
-  if (a.kvol <= 32 && ks == 2) {
-    hipLaunchKernelGGL((conv_fwd_kernel<NT, 32, 2>), dim3((unsigned)ceil_div(a.m_out, 32), nblk_y), dim3(256), 0, stream, a);
-    return;
-  }
-  if (a.kvol <= 32 && ks == 4) {
-    hipLaunchKernelGGL((conv_fwd_kernel<NT, 32, 4>), dim3((unsigned)ceil_div(a.m_out, 16), nblk_y), dim3(256), 0, stream, a);
-    return;
-  }
-  const unsigned gx = (unsigned)ceil_div(a.m_out, 64);
-  if (a.kvol <= 32) hipLaunchKernelGGL((conv_fwd_kernel<NT, 32>), dim3(gx, nblk_y), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((conv_fwd_kernel<NT, kMaxKvol>), dim3(gx, nblk_y), dim3(256), 0, stream, a);
-}
-
-int run_conv(const float* in, int64_t m_in, int cin, const float* wp, const float* bias, int cout, int kvol,
-             const int* nbr, int64_t m_out, float* out, hipStream_t stream, const int* order = nullptr) {
-  EFG_CHECK_ARG(cin >= 1 && cout >= 1, "spconv: bad channel counts");
-  EFG_CHECK_ARG(kvol >= 1 && kvol <= kMaxKvol, "spconv: kernel volume must be in [1,%d], got %d", kMaxKvol, kvol);
-  if (m_out == 0) return EFG_OK;
-  EFG_CHECK_ARG(m_in >= 0 && (unsigned long long)m_in * (unsigned long long)cin * 4ull < (1ull << 32),
-                "spconv: input features of %lld x %d floats exceed the 4 GB the gather addresses", (long long)m_in, cin);
-  ConvArgs a;
-  a.in = in;
-  a.wp = wp;
-  a.bias = bias;
-  a.nbr = nbr;
-  a.out = out;
-  a.order = order;
-  a.m_out = m_out;
-  a.cin = cin;
-  a.cout = cout;
-  a.kvol = kvol;
-  a.c16n = (cin + 15) / 16;
-  a.np = (cout + 15) / 16 * 16;
-  const int ntiles = a.np / 16;
-  // n-tiles per wave (NT): as many as possible (A-tile reuse) while the launch still has >= ~2 waves
-  // per SIMD on the whole chip; small levels (a few thousand rows x 256 channels) otherwise run one
-  // long serial MFMA chain per wave on a third of the CUs.  Wider outputs tile over grid.y.
-  const long long row_waves = ceil_div(m_out, 16);
-  int nt = 16;
-  // With the kernel offsets split over the 4 waves of a workgroup (KS, below) a row tile already is 4 waves, so the
-  // 3x3x3 layers fill the chip with fewer tiles: 1400 instead of 2048 lets the 256-channel layers (371 row tiles) take
-  // 4 n-tiles per wave instead of 2 -- half the gathers per MFMA: 205 -> 170 us, 60 -> 72 TFLOP/s.
-  constexpr int ks_env = 4;
-  const long long fill = (kvol >= 8 && ks_env > 1) ? 1400 : 2048;
-  while (nt > 1 && (nt / 2 >= ntiles || row_waves * ((ntiles + nt - 1) / nt) < fill)) nt >>= 1;
-  if (nt > ntiles) nt = ntiles >= 16 ? 16 : ntiles >= 8 ? 8 : ntiles >= 4 ? 4 : ntiles >= 2 ? 2 : 1;
-  while (nt < ntiles && nt < 16 && (ntiles % nt) != 0) nt <<= 1;  // keep grid.y exact where possible
-  const int ny = (ntiles + nt - 1) / nt;
-  // split-K over the 4 waves of a workgroup for the 3x3x3 kernels with 2-4 n-tiles per wave (measured -10 %);
-  // 16-channel outputs (NT = 1) and the 3-offset z-collapsing heads gain nothing.  EFG_CONV_KS overrides (1 | 2 | 4).
-  const int ks = (kvol >= 8) ? ks_env : 1;
-  switch (nt) {
-    case 16: launch_fwd<16>(a, ny, 1, stream); break;
-    case 8: launch_fwd<8>(a, ny, 1, stream); break;
-    case 4: launch_fwd<4>(a, ny, ks, stream); break;
-    case 2: launch_fwd<2>(a, ny, ks, stream); break;
-    default: launch_fwd<1>(a, ny, 1, stream); break;
-  }
-  EFG_LAUNCH_CHECK();
-  return EFG_OK;
-}
-
 }  // namespace
 }  // namespace efg
 
@@ -725,7 +430,7 @@ extern "C" size_t efg_spconv_packed_weight_bytes(int cout, int kvol, int cin, in
   if (cout < 1 || cin < 1 || kvol < 1) return 0;
   for_dgrad &= 1;  // (bit 2, the bf16x3 layout, is the same size)
   const int red = for_dgrad ? cout : cin, nn = for_dgrad ? cin : cout;
-  // + one tile row of slack: kernels with NT > tiles read (zero-weight) past the last n-tile
+  // + one tile row of slack: conv_tile_kernel (spconv_tiles.hip) reads (zero-weight) past the last n-tile when NT does not divide the tiles
   return ((size_t)kvol * ((red + 15) / 16) * ((nn + 15) / 16 * 16) * 16 + 16 * 256) * sizeof(float);
 }
 
@@ -759,117 +464,6 @@ extern "C" int efg_spconv_pack_weights_multi(const void* items_dev, int n, void*
   return EFG_OK;
 }
 
-extern "C" int efg_spconv_forward_f32(const float* in_feat, int64_t m_in, int cin, const float* packed_weight,
-                                      const float* bias, int cout, int kvol, const int32_t* nbr, int64_t m_out,
-                                      float* out_feat, void* stream) {
-  return run_conv(in_feat, m_in, cin, packed_weight, bias, cout, kvol, nbr, m_out, out_feat, (hipStream_t)stream);
-}
-
-extern "C" int efg_spconv_dgrad_f32(const float* grad_out, int64_t m_out, int cout, const float* packed_weight,
-                                    int cin, int kvol, const int32_t* rnbr, int64_t m_in, const int32_t* row_order,
-                                    float* grad_in, void* stream) {
-  return run_conv(grad_out, m_out, cout, packed_weight, nullptr, cin, kvol, rnbr, m_in, grad_in, (hipStream_t)stream,
-                  row_order);
-}
-
-// ---- row order by coordinate parity ---------------------------------------------------------------------------
-// The dgrad of a stride-2 convolution computes one row per FINE site, and which of the 27 offsets reach a parent
-// depends only on the parity of the site's (z, y, x): 8 classes with ~3.4 offsets each.  Neighbouring rows of the
-// canonical order differ in parity, so a 16-row tile runs ~10 offsets (scripts/ubench/tile_waste.py: x2.9).  This
-// orders the rows by class (within a class in the order the waves arrive, i.e. roughly spatially); results do not
-// depend on the order -- a row's sum runs over its own offsets in ascending k whatever its tile mates are.
-namespace efg {
-namespace {
-__device__ __forceinline__ int parity_class(const int* __restrict__ idx, long long r) {
-  const int4 v = *reinterpret_cast<const int4*>(idx + r * 4);  // (b, z, y, x)
-  return ((v.y & 1) << 2) | ((v.z & 1) << 1) | (v.w & 1);
-}
-
-constexpr int kParRows = 1024;  // rows per workgroup (4 per thread)
-
-// class totals: ballots -> LDS counters -> 8 global atomics per workgroup (one atomic per wave and class on 8 shared
-// addresses took 27 us for 117k rows)
-__global__ void __launch_bounds__(256) parity_count_kernel(const int* __restrict__ idx, long long m, int* __restrict__ counts) {
-  __shared__ int sc[8];
-  const int lane = threadIdx.x & 63;
-  if (threadIdx.x < 8) sc[threadIdx.x] = 0;
-  __syncthreads();
-  const long long r0 = (long long)blockIdx.x * kParRows;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const long long r = r0 + j * 256 + threadIdx.x;
-    const int c = r < m ? parity_class(idx, r) : -1;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const unsigned long long bal = __ballot(c == k);
-      if (lane == 0 && bal) atomicAdd(&sc[k], __popcll(bal));
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 8 && sc[threadIdx.x]) atomicAdd(&counts[threadIdx.x], sc[threadIdx.x]);
-}
-
-// a workgroup reserves one range per class (8 global atomics), its waves take sub-ranges from LDS cursors
-__global__ void __launch_bounds__(256) parity_scatter_kernel(const int* __restrict__ idx, long long m, const int* __restrict__ counts,
-                                                              int* __restrict__ cursor, int* __restrict__ order) {
-  __shared__ int sc[8], sbase[8], scur[8];
-  const int lane = threadIdx.x & 63;
-  if (threadIdx.x < 8) sc[threadIdx.x] = 0;
-  __syncthreads();
-  const long long r0 = (long long)blockIdx.x * kParRows;
-  int cls[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const long long r = r0 + j * 256 + threadIdx.x;
-    cls[j] = r < m ? parity_class(idx, r) : -1;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const unsigned long long bal = __ballot(cls[j] == k);
-      if (lane == 0 && bal) atomicAdd(&sc[k], __popcll(bal));
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 8) {
-    int before = 0;
-    for (int k = 0; k < (int)threadIdx.x; ++k) before += counts[k];
-    sbase[threadIdx.x] = before + (sc[threadIdx.x] ? atomicAdd(&cursor[threadIdx.x], sc[threadIdx.x]) : 0);
-    scur[threadIdx.x] = 0;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const long long r = r0 + j * 256 + threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const unsigned long long bal = __ballot(cls[j] == k);
-      if (bal) {
-        int start = 0;
-        if (lane == 0) start = atomicAdd(&scur[k], __popcll(bal));
-        start = __shfl(start, 0, 64);
-        if (cls[j] == k) order[sbase[k] + start + __popcll(bal & ((1ull << lane) - 1ull))] = (int)r;
-      }
-    }
-  }
-}
-}  // namespace
-}  // namespace efg
-
-extern "C" int efg_spconv_parity_order(const int32_t* indices, int64_t m, int32_t* order, void* ws, size_t ws_bytes,
-                                       void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  EFG_CHECK_ARG(m >= 0 && m < (1ll << 31), "parity_order: bad row count");
-  if (m == 0) return EFG_OK;
-  EFG_CHECK_ARG(indices && order && ws && ws_bytes >= 64, "parity_order: null pointer / workspace < 64 bytes");
-  int* counts = static_cast<int*>(ws);
-  EFG_HIP_TRY(hipMemsetAsync(counts, 0, 64, stream));
-  const int blocks = (int)ceil_div(m, kParRows);
-  hipLaunchKernelGGL(parity_count_kernel, dim3(blocks), dim3(256), 0, stream, indices, (long long)m, counts);
-  hipLaunchKernelGGL(parity_scatter_kernel, dim3(blocks), dim3(256), 0, stream, indices, (long long)m, counts, counts + 8,
-                     order);
-  EFG_LAUNCH_CHECK();
-  return EFG_OK;
-}
-
 extern "C" size_t efg_spconv_wgrad_workspace_bytes(int64_t m_out, int cin, int cout, int kvol) {
   if (cin < 1 || cout < 1 || kvol < 1 || m_out < 0) return 0;
   return wgrad_plan(m_out, cin, cout, kvol).bytes + 256;
@@ -879,7 +473,7 @@ extern "C" int efg_spconv_wgrad_f32(const float* in_feat, int64_t m_in, int cin,
                                     int64_t m_out, int cout, int kvol, const int32_t* nbr, float* grad_w, void* ws,
                                     size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  EFG_CHECK_ARG(cin >= 1 && cout >= 1 && kvol >= 1 && kvol <= kMaxKvol, "spconv wgrad: bad sizes");
+  EFG_CHECK_ARG(cin >= 1 && cout >= 1 && kvol >= 1 && kvol <= kSpconvMaxKvol, "spconv wgrad: bad sizes");
   EFG_CHECK_ARG(m_in >= 0 && (unsigned long long)m_in * cin * 4ull < (1ull << 32) &&
                     (unsigned long long)(m_out > 0 ? m_out : 0) * cout * 4ull < (1ull << 32),
                 "spconv wgrad: feature tensors must be smaller than 4 GB");

@@ -1,8 +1,11 @@
-// Sparse convolution, second generation: MASK-SORTED ROW TILES.
+// Sparse convolution forward / data gradient over MASK-SORTED ROW TILES: output-stationary gathered implicit GEMM,
+//     out[o][:] = sum_k  in[nbr[k][o]][:] . W[:,k,:]^T
+// with every output row produced once (no scatter, no atomics); the data gradient is the same kernel over the transposed
+// table and transposed weights.
 //
-// The output-stationary kernel of spconv_conv.hip takes 16 consecutive rows (canonical spatial order) per wave and
-// executes every kernel offset ANY of the 16 rows needs: measured x1.35 the useful MFMAs on the submanifold layers,
-// x2.1 on the strided forwards (scripts/ubench/tile_waste.py; profiles/r02_*).  Which offsets a row needs is its
+// A wave that takes 16 consecutive rows (canonical spatial order) executes every kernel offset ANY of the 16 rows
+// needs: measured x1.35 the useful MFMAs on the submanifold layers, x2.1 on the strided forwards (the first kernel of
+// this project worked that way: scripts/ubench/tile_waste.py; profiles/r02_*).  Which offsets a row needs is its
 // 27-bit neighbour mask, and rows with equal masks are plentiful (ground, walls: a few hundred patterns cover a
 // level) but interleaved in space.  A *tile plan* therefore re-orders the rows of a neighbour table inside chunks of
 // 1024 consecutive rows by their mask (an LDS bitonic sort of {mask, row}), cuts the sorted sequence into 16-row
@@ -11,10 +14,10 @@
 // three z-slabs of ~1k rows).  The plan depends only on geometry: it is built once per rulebook on the geometry
 // stream and shared by every convolution, direction and training step that uses the table (9 launches for a res18
 // submanifold key).  A row's sum runs over ITS offsets only; the plan is a pure function of the table, so results are
-// reproducible run to run (with KS > 1 the grouping of a row's partial sums follows its tile, as in generation one).
+// reproducible run to run (with KS > 1 the grouping of a row's partial sums follows its tile).
 //
 // Kernel (conv_tile_kernel): per wave R sub-tiles of 16 rows (R = 2: one B fragment load feeds two row tiles, which
-// halves the weight traffic through the vector L1 -- PMC: 52 % of the L1's peak bandwidth in generation one), NT
+// halves the weight traffic through the vector L1 -- PMC: 52 % of the L1's peak bandwidth in that first kernel, one row tile per load), NT
 // output-channel tiles, v_mfma_f32_16x16x4_f32, A through a wave-private LDS tile, next gather in flight during the
 // MFMAs; the offsets of a tile are split over the KS waves of its workgroup and summed through LDS (small levels).
 // The prologue is three coalesced loads (rows, neighbour block, masks) -- no ballots, no index arithmetic.
@@ -934,7 +937,7 @@ int streamk_for_stream(hipStream_t stream, StreamKState** out) {
 bool bf16x3_ok(int cin, int cout, int kvol, int64_t m_in, int64_t m_out) {
   int nt, r, ks;
   tile_shape(cin, cout, kvol, m_in, m_out, &nt, &r, &ks);
-  return nt == 4 && ks == 4 && kvol <= 31 && cin >= 64 && cin % 32 == 0 && cout % 64 == 0;
+  return nt == 4 && ks == 4 && kvol <= kSpconvMaxKvol && cin >= 64 && cin % 32 == 0 && cout % 64 == 0;
 }
 
 // conv_small_kernel covers a (cin -> cout, kvol) layer with 16 or 32 reduction channels (16-byte pieces) or at most 8 (4-byte
@@ -962,7 +965,7 @@ int run_tiles(const float* in, int64_t m_in, int cin, const float* wp, const flo
   EFG_CHECK_ARG(!bf3 || bf16x3_ok(cin, cout, kvol, m_in, m_out),
                 "spconv tiled: the bf16x3 arm does not cover %d -> %d channels, kvol %d (ask efg_spconv_tile_bf16x3_ok)", cin,
                 cout, kvol);
-  EFG_CHECK_ARG(kvol >= 1 && kvol <= 31, "spconv tiled: kernel volume must be in [1,31], got %d", kvol);
+  EFG_CHECK_ARG(kvol >= 1 && kvol <= kSpconvMaxKvol, "spconv tiled: kernel volume must be in [1,%d], got %d", kSpconvMaxKvol, kvol);
   if (m_out == 0) return EFG_OK;
   EFG_CHECK_ARG(m_in >= 0 && (unsigned long long)m_in * (unsigned long long)cin * 4ull < (1ull << 32),
                 "spconv tiled: input features of %lld x %d floats exceed the 4 GB the gather addresses", (long long)m_in, cin);
@@ -1091,14 +1094,14 @@ int run_tiles(const float* in, int64_t m_in, int cin, const float* wp, const flo
 using namespace efg;
 
 extern "C" size_t efg_spconv_tile_plan_bytes(int64_t m, int kvol) {
-  if (m < 0 || kvol < 1 || kvol > 31) return 0;
+  if (m < 0 || kvol < 1 || kvol > kSpconvMaxKvol) return 0;
   return plan_bytes(m, kvol) + 256;
 }
 
 extern "C" int efg_spconv_tile_plan(const int32_t* nbr, int64_t m, int kvol, void* plan, size_t plan_bytes_given,
                                     void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  EFG_CHECK_ARG(m >= 0 && m < (1ll << 31) && kvol >= 1 && kvol <= 31, "tile_plan: bad sizes (m=%lld, kvol=%d)", (long long)m, kvol);
+  EFG_CHECK_ARG(m >= 0 && m < (1ll << 31) && kvol >= 1 && kvol <= kSpconvMaxKvol, "tile_plan: bad sizes (m=%lld, kvol=%d)", (long long)m, kvol);
   if (m == 0) return EFG_OK;
   EFG_CHECK_ARG(nbr && plan && plan_bytes_given >= plan_bytes(m, kvol), "tile_plan: null pointer / plan buffer too small");
   const PlanView pv = plan_view(plan, m, kvol);

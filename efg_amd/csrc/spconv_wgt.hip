@@ -4,7 +4,8 @@
 // (reference: spconv's indice-conv backward -- the pair-gathered GEMM  dW_k = G_pairs^T . X_pairs  per kernel offset,
 // called from efg/modeling/backbones/sparse_net.py through spconv.SparseConv3d / SubMConv3d).
 //
-// The first-generation kernel (spconv_conv.hip: conv_wgrad_kernel) walks the neighbour table, compacts the valid
+// The table-walking kernel (spconv_conv.hip: conv_wgrad_kernel, which stays for the widths this one does not cover and
+// as the reference this one is tested against) walks the neighbour table, compacts the valid
 // (out row, in row) pairs of 256 rows through an LDS queue with ballots and workgroup barriers, stages 32-pair tiles
 // of both operands in LDS and reads MFMA fragments back: three barriers per 1024 MFMA cycles, 0.31 of the fp32 MFMA
 // peak in the training step.  Here the reduction dimension of the product IS the row dimension, so a 16-row tile of
@@ -432,7 +433,7 @@ __global__ void __launch_bounds__(256) wgt_reduce_kernel(const float* __restrict
 // res34 and CenterPoint backbones.
 bool wgt_width_ok(int c) { return c == 16 || c == 32 || (c >= 64 && c % 64 == 0); }
 bool wgt_ok(int cin, int cout, int kvol) {
-  return kvol >= 1 && kvol <= 31 && wgt_width_ok(cout) && ((cin >= 1 && cin <= 16) || wgt_width_ok(cin));
+  return kvol >= 1 && kvol <= kSpconvMaxKvol && wgt_width_ok(cout) && ((cin >= 1 && cin <= 16) || wgt_width_ok(cin));
 }
 inline int wgt_tiles(int c) { return c >= 64 ? 4 : (c + 15) / 16; }   // 16-channel tiles of a block along one side
 inline int wgt_cin_pad(int cin) { return cin < 16 ? 16 : cin; }

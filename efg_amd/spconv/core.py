@@ -4,7 +4,7 @@ The reference backbone (efg/modeling/backbones/sparse_net.py:6-11) imports third
 `spconv.pytorch`; this module provides the subset it calls -- `SparseConvTensor`, `SparseModule`,
 `SparseSequential`, `SubMConv3d`, `SparseConv3d`, `.dense()`, `.replace_feature()` -- with spconv
 2.x constructor signatures and parameter layout (`weight` is [Cout, kd, kh, kw, Cin]), on top of
-the HIP kernels in csrc/spconv_index.hip and csrc/spconv_conv.hip.
+the HIP kernels in csrc/spconv_index.hip, spconv_tiles.hip, spconv_wgt.hip and spconv_conv.hip.
 
 Semantics: SubMConv3d keeps the input's sites AND row order; SparseConv3d activates
 every output site touched by an input site and returns rows in canonical order (ascending
@@ -21,6 +21,8 @@ from torch.autograd.function import once_differentiable
 
 from .. import _lib as L
 from .. import _prof
+
+MAX_KERNEL_VOLUME = 31   # offsets of a window: the library's limit (csrc/common.h: kSpconvMaxKvol), checked when a layer is built
 
 
 def _triple(v):
@@ -99,7 +101,7 @@ def _build_plan(table, m, kvol):
     lib = L.lib()
     nbytes = lib.efg_spconv_tile_plan_bytes(m, kvol)
     if nbytes == 0:
-        raise RuntimeError("efg_hip: tile plan needs kvol <= 31, got %d" % kvol)
+        raise RuntimeError("efg_hip: tile plan needs kvol <= %d, got %d" % (MAX_KERNEL_VOLUME, kvol))
     plan = torch.empty(nbytes, dtype=torch.uint8, device=table.device)
     L.check(lib.efg_spconv_tile_plan(L.ptr(table), m, kvol, L.ptr(plan), nbytes, L.stream()))
     return plan
@@ -129,7 +131,7 @@ def _wgrad_tiled(cin, cout, kvol, m_out, m_in=0):
     key = (cin, cout, kvol)
     ok = _WGT_OK.get(key)
     if ok is None:
-        ok = _WGT_OK[key] = (kvol <= 31 and os.environ.get("EFG_WGRAD_TILED", "1") != "0"
+        ok = _WGT_OK[key] = (os.environ.get("EFG_WGRAD_TILED", "1") != "0"
                              and bool(L.lib().efg_spconv_wgrad_tiled_ok(cin, cout, kvol)))
     return ok
 
@@ -247,42 +249,26 @@ def _conv_forward(features, w, bias, rb, owner=None):
     """features [m_in,cin], w [cout,kvol,cin] -> [m_out,cout]"""
     lib = L.lib()
     cout, kvol, cin = w.shape
-    # mask-sorted row tiles (csrc/spconv_tiles.hip) for every window of at most 31 offsets; the generation-one kernels
-    # (csrc/spconv_conv.hip) remain for larger windows and empty tables (profiles/r02_gen1_vs_tiled_per_layer.txt)
-    tiled = kvol <= 31 and rb.m_out > 0
-    arm = _arm_bf16x3(cin, cout, kvol, rb.m_in, rb.m_out) if tiled else 0   # (4 in the flag word: the split-precision arm)
+    arm = _arm_bf16x3(cin, cout, kvol, rb.m_in, rb.m_out)   # (4 in the flag word: the split-precision arm)
     packed = _packed_weight(w, 0 | arm, owner)
     out = torch.empty((rb.m_out, cout), dtype=torch.float32, device=features.device)
-    if tiled:
-        plan = rb.plan_fwd()
-        with _prof.timed(_tile_kernel_name(cin, cout, kvol, rb.m_in, rb.m_out), _Cost(rb, cin, cout, "fwd")):
-            L.check(lib.efg_spconv_forward_tiled_f32(L.ptr(features), rb.m_in, cin, L.ptr(packed), L.ptr(bias), cout,
-                                                     kvol, L.ptr(plan), rb.m_out, 0 | arm, L.ptr(out), L.stream()))
-        return out
-    with _prof.timed(_fwd_kernel_name(cout, rb.m_out, kvol), _Cost(rb, cin, cout, "fwd")):
-        L.check(lib.efg_spconv_forward_f32(L.ptr(features), rb.m_in, cin, L.ptr(packed), L.ptr(bias), cout, kvol,
-                                           L.ptr(rb.nbr), rb.m_out, L.ptr(out), L.stream()))
+    plan = rb.plan_fwd()   # (None for an empty table: the library returns before it reads a plan)
+    with _prof.timed(_tile_kernel_name(cin, cout, kvol, rb.m_in, rb.m_out), _Cost(rb, cin, cout, "fwd")):
+        L.check(lib.efg_spconv_forward_tiled_f32(L.ptr(features), rb.m_in, cin, L.ptr(packed), L.ptr(bias), cout,
+                                                 kvol, L.ptr(plan), rb.m_out, 0 | arm, L.ptr(out), L.stream()))
     return out
 
 
 def _conv_dgrad(grad_out, w, rb, owner=None):
     lib = L.lib()
     cout, kvol, cin = w.shape
-    tiled = kvol <= 31 and rb.m_in > 0
-    arm = _arm_bf16x3(cout, cin, kvol, rb.m_out, rb.m_in) if tiled else 0
+    arm = _arm_bf16x3(cout, cin, kvol, rb.m_out, rb.m_in)
     packed = _packed_weight(w, 1 | arm, owner)
     grad_in = torch.empty((rb.m_in, cin), dtype=torch.float32, device=grad_out.device)
-    if tiled:
-        plan, flip = rb.plan_dgrad()
-        with _prof.timed(_tile_kernel_name(cout, cin, kvol, rb.m_out, rb.m_in), _Cost(rb, cin, cout, "dgrad")):
-            L.check(lib.efg_spconv_forward_tiled_f32(L.ptr(grad_out), rb.m_out, cout, L.ptr(packed), None, cin, kvol,
-                                                     L.ptr(plan), rb.m_in, flip | arm, L.ptr(grad_in), L.stream()))
-        return grad_in
-    rnbr = rb.rnbr
-    order = rb.dgrad_order()
-    with _prof.timed(_fwd_kernel_name(cin, rb.m_in, kvol), _Cost(rb, cin, cout, "dgrad")):
-        L.check(lib.efg_spconv_dgrad_f32(L.ptr(grad_out), rb.m_out, cout, L.ptr(packed), cin, kvol, L.ptr(rnbr),
-                                         rb.m_in, L.ptr(order), L.ptr(grad_in), L.stream()))
+    plan, flip = rb.plan_dgrad()
+    with _prof.timed(_tile_kernel_name(cout, cin, kvol, rb.m_out, rb.m_in), _Cost(rb, cin, cout, "dgrad")):
+        L.check(lib.efg_spconv_forward_tiled_f32(L.ptr(grad_out), rb.m_out, cout, L.ptr(packed), None, cin, kvol,
+                                                 L.ptr(plan), rb.m_in, flip | arm, L.ptr(grad_in), L.stream()))
     return grad_in
 
 
@@ -310,7 +296,7 @@ def _conv_wgrad(features, grad_out, rb):
 def _pair_ok(rb, w_a, w_b, cin, cout):
     """Can the two convolutions (weights [cout, kvol, cin] each) over `rb` run as the pair launches of csrc/spconv_tiles.hip /
     spconv_wgt.hip?  (the tiled fp32 path with the default weight order; EFG_CONV_PAIR=0: two launches each, A/B)"""
-    return (os.environ.get("EFG_CONV_PAIR", "1") != "0" and rb.kvol <= 31 and rb.m_out > 0 and rb.m_in > 0
+    return (os.environ.get("EFG_CONV_PAIR", "1") != "0" and rb.m_out > 0 and rb.m_in > 0
             and w_a.shape == w_b.shape
             and not _arm_bf16x3(cin, cout, rb.kvol, rb.m_in, rb.m_out) and not _arm_bf16x3(cout, cin, rb.kvol, rb.m_out, rb.m_in))
 
@@ -354,21 +340,6 @@ def _conv_wgrad_pair(features, go_a, go_b, rb):
                                                     L.ptr(plan), L.ptr(sched), L.ptr(gw_a), L.ptr(gw_b), L.ptr(ws), ws_bytes,
                                                     L.stream()))
     return gw_a, gw_b
-
-
-def _fwd_kernel_name(n_out_channels, n_rows, kvol=27):
-    """Symbol of the forward/dgrad instantiation csrc/spconv_conv.hip:run_conv picks (same rule)."""
-    ntiles = (n_out_channels + 15) // 16
-    row_waves = (n_rows + 15) // 16
-    fill = 1400 if kvol >= 8 else 2048
-    nt = 16
-    while nt > 1 and (nt // 2 >= ntiles or row_waves * ((ntiles + nt - 1) // nt) < fill):
-        nt >>= 1
-    if nt > ntiles:
-        nt = 16 if ntiles >= 16 else 8 if ntiles >= 8 else 4 if ntiles >= 4 else 2 if ntiles >= 2 else 1
-    while nt < ntiles and nt < 16 and ntiles % nt != 0:
-        nt <<= 1
-    return "conv_fwd_kernel<%d>" % nt
 
 
 class _Cost:
@@ -489,13 +460,11 @@ def _hand_over(main, *tensors):
 class Rulebook:
     """Output-stationary neighbour table of one convolution geometry."""
 
-    def __init__(self, nbr, m_in, m_out, kvol, subm, in_indices=None):
+    def __init__(self, nbr, m_in, m_out, kvol, subm):
         self.nbr = nbr          # int32 [kvol, m_out]
         self.m_in, self.m_out, self.kvol, self.subm = m_in, m_out, kvol, subm
-        self.in_indices = in_indices  # int32 [m_in, 4] of a strided geometry (for the dgrad row order)
         self._rnbr = None
         self._pairs = None
-        self._order = None
         self._plan_fwd = None
         self._plan_stream = None
         self._plan_dgrad = None
@@ -555,20 +524,6 @@ class Rulebook:
                 self._plan_dgrad = _build_plan(rnbr, self.m_in, self.kvol)
                 _hand_over(main, self._plan_dgrad)
         return self._plan_dgrad, 0
-
-    def dgrad_order(self):
-        """int32 [m_in] row order for the dgrad of a strided geometry: input rows grouped by coordinate parity, so the
-        16 rows of a tile share their reachable offsets (csrc/spconv_conv.hip: efg_spconv_parity_order); None for
-        submanifold geometries (every row reaches every offset)."""
-        if self.subm or self.in_indices is None or self.m_in == 0:
-            return None
-        if self._order is None:
-            idx = self.in_indices
-            order = torch.empty(self.m_in, dtype=torch.int32, device=idx.device)
-            ws = torch.empty(64, dtype=torch.uint8, device=idx.device)
-            L.check(L.lib().efg_spconv_parity_order(L.ptr(idx), self.m_in, L.ptr(order), L.ptr(ws), 64, L.stream()))
-            self._order = order
-        return self._order
 
     @property
     def rnbr(self):
@@ -995,6 +950,9 @@ class SparseConvolution(SparseModule):
         assert _triple(dilation) == (1, 1, 1), "dilation is not used by the EFG backbones"
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride, self.padding = _triple(kernel_size), _triple(stride), _triple(padding)
+        if math.prod(self.kernel_size) > MAX_KERNEL_VOLUME:
+            raise ValueError("SparseConvolution: a %d x %d x %d window has %d offsets, the kernels take at most %d"
+                             % (*self.kernel_size, math.prod(self.kernel_size), MAX_KERNEL_VOLUME))
         self.subm, self.indice_key = subm, indice_key
         if subm:
             assert self.stride == (1, 1, 1) and all(k % 2 == 1 for k in self.kernel_size)
@@ -1049,7 +1007,7 @@ class SparseConvolution(SparseModule):
             m_out = out_indices.shape[0]
             nbr = _build_nbr(si, out_indices, m_out, ks, st, pad)
             _hand_over(main, nbr, out_indices, out_site_index.index, si.index, si.perm)
-        rb = Rulebook(nbr, x.indices.shape[0], m_out, nbr.shape[0], False, in_indices=x.indices)
+        rb = Rulebook(nbr, x.indices.shape[0], m_out, nbr.shape[0], False)
         geom = (out_indices, out_site_index, oshape_py)
         x._conv_cache[key] = (rb, geom)
         return rb, geom

@@ -179,16 +179,6 @@ int efg_spconv_pack_weight_f32(const float* weight, int cout, int kvol, int cin,
  * (the model's layers change together at the optimizer step: their packed copies are refreshed together). */
 int efg_spconv_pack_weights_multi(const void* items_dev, int n, void* stream);
 
-/* out[o][:] = bias + sum_k W[:,k,:] . in[nbr[k][o]][:]   (bias may be NULL; packed: for_dgrad = 0) */
-int efg_spconv_forward_f32(const float* in_feat, int64_t m_in, int cin, const float* packed_weight,
-                           const float* bias, int cout, int kvol, const int32_t* nbr, int64_t m_out,
-                           float* out_feat, void* stream);
-/* grad_in[i][:] = sum_k W[:,k,:]^T . grad_out[rnbr[k][i]][:]   (packed: for_dgrad = 1).
- * row_order: NULL, or a permutation of the m_in rows (efg_spconv_parity_order): workgroup tiles take their 16 rows
- * in that order; the result does not depend on it. */
-int efg_spconv_dgrad_f32(const float* grad_out, int64_t m_out, int cout, const float* packed_weight, int cin,
-                         int kvol, const int32_t* rnbr, int64_t m_in, const int32_t* row_order, float* grad_in,
-                         void* stream);
 /* ---- mask-sorted row tiles (csrc/spconv_tiles.hip) ------------------------------------------------------------
  * A tile plan of a neighbour table `nbr` [kvol][m]: the rows re-ordered inside chunks of 1024 consecutive rows by
  * their kernel-offset mask, cut into 16-row tiles, with the neighbour columns in tile-major order and per-offset
@@ -197,7 +187,8 @@ int efg_spconv_dgrad_f32(const float* grad_out, int64_t m_out, int cout, const f
  * reference tree; call sites efg/modeling/backbones/sparse_net.py:85-95,125-147). */
 size_t efg_spconv_tile_plan_bytes(int64_t m, int kvol);
 int efg_spconv_tile_plan(const int32_t* nbr, int64_t m, int kvol, void* plan, size_t plan_bytes, void* stream);
-/* out[o][:] = bias + sum_k W[:,k,:] . in[nbr[k][o]][:] over the plan of nbr.  flip_offsets = 1 pairs table column c
+/* out[o][:] = bias + sum_k W[:,k,:] . in[nbr[k][o]][:] over the plan of nbr (bias may be NULL; packed: for_dgrad = 0).
+ * m_out == 0 returns at once without reading the plan (which may then be NULL).  flip_offsets = 1 pairs table column c
  * with weight offset kvol-1-c: the dgrad of a submanifold conv on the FORWARD table's plan (packed: for_dgrad = 1,
  * in = grad_out, cin/cout swapped by the caller), since the transposed table of a symmetric window is the table
  * with its offsets reversed.  The dgrad of a strided conv passes the plan of its transposed table and flip 0.
@@ -249,10 +240,7 @@ int efg_spconv_small_ok(int cin, int cout, int kvol, int* c16, int* nt);
 /* 1 when the split-precision arm of the tile kernel covers a (cin -> cout, kvol) convolution of these table sizes. */
 int efg_spconv_tile_bf16x3_ok(int cin, int cout, int kvol, int64_t m_in, int64_t m_out);
 
-/* order[m]: the rows of `indices` (int32 [m][4] = b, z, y, x) grouped by the parity of (z, y, x) -- the rows of a
- * stride-2 layer's dgrad that share their set of reachable kernel offsets.  ws: 64 bytes. */
-int efg_spconv_parity_order(const int32_t* indices, int64_t m, int32_t* order, void* ws, size_t ws_bytes,
-                            void* stream);
+/* The weight gradient straight from the neighbour table (csrc/spconv_conv.hip): any channel widths, kvol <= 31. */
 size_t efg_spconv_wgrad_workspace_bytes(int64_t m_out, int cin, int cout, int kvol);
 /* grad_w[cout][kvol][cin] = sum_o grad_out[o]^T (x) in[nbr[k][o]]  (deterministic two-pass) */
 int efg_spconv_wgrad_f32(const float* in_feat, int64_t m_in, int cin, const float* grad_out, int64_t m_out,

@@ -14,12 +14,9 @@ for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
     with open("%s/%s.summary.csv" % (src, ctr)) as f:
         for row in csv.DictReader(f):
             name = row["kernel"].replace("efg::", "").replace(";", ",")
-            # bench.py labels: conv_fwd_kernel<NT> -- the KV / KS template arguments are launch details; variants of
-            # one NT are merged with a launch-weighted mean
-            m = re.match(r"conv_fwd_kernel<(\d+), \d+(, \d+)?>$", name)
-            if m:
-                name = "conv_fwd_kernel<%s>" % m.group(1)
-            m = re.match(r"conv_tile_kernel<(\d+), \d+, \d+(, \d+){0,2}>$", name)  # <NT, R, KS, MODE> (older profiles: <NT, R, KS[, V4[, MODE]]>): bench.py labels by NT
+            # bench.py labels: conv_tile_kernel<NT> -- the other template arguments are launch details; variants of one NT
+            # are merged with a launch-weighted mean
+            m = re.match(r"conv_tile_kernel<(\d+), \d+, \d+(, \d+){0,2}>$", name)  # <NT, R, KS, MODE> (older profiles: <NT, R, KS[, V4[, MODE]]>)
             if m:
                 name = "conv_tile_kernel<%s>" % m.group(1)
             m = re.match(r"(box_bwd_tile_[ab]_kernel)<\d+>$", name)   # counter files from when the tile height was a template argument

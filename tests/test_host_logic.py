@@ -166,3 +166,16 @@ def test_bench_bare_multi_gpu_command_names_the_missing_devices():
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode != 0
     assert "needs %d devices" % n in r.stderr, r.stderr[-2000:]
+
+
+def test_sparse_conv_window_limit_is_checked_when_the_layer_is_built():
+    """A sparse-convolution window has at most 31 offsets (the tile plan's mask word); a larger one is refused by the
+    layer's constructor, naming the window and the limit, not at the first forward pass."""
+    from efg_amd.spconv import SparseConv3d, SubMConv3d
+
+    with pytest.raises(ValueError, match=r"4 x 4 x 2 window has 32 offsets.* 31\b"):
+        SparseConv3d(4, 8, (4, 4, 2))
+    with pytest.raises(ValueError, match=r"3 x 3 x 5 window has 45 offsets.* 31\b"):
+        SubMConv3d(4, 8, (3, 3, 5))
+    assert SubMConv3d(4, 8, 3).weight.shape == (8, 3, 3, 3, 4)
+    assert SparseConv3d(4, 8, (3, 1, 1), (2, 1, 1)).weight.shape == (8, 3, 1, 1, 4)

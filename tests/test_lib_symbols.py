@@ -38,6 +38,9 @@ def test_version_and_error_channel(lib):
     assert lib.efg_hard_voxelize_workspace_bytes(180000, 2, 5, 5, 120000, vs, cr) > 0
     assert lib.efg_spconv_packed_weight_bytes(64, 27, 64, 0) >= 27 * 64 * 64 * 4
     assert lib.efg_spconv_wgrad_workspace_bytes(100000, 64, 64, 27) > 0
+    # a sparse-convolution window has at most 31 offsets: one limit for the plan, the tiles and both weight gradients
+    assert lib.efg_spconv_tile_plan_bytes(1000, 32) == 0
+    assert lib.efg_spconv_wgrad_tiled_ok(64, 64, 32) == 0
     shp = (ctypes.c_int * 3)(41, 1504, 1504)
     assert lib.efg_spconv_index_bytes(2, shp) == ((2 * 41 * 1504 * 1504 + 31) // 32) * 8
     big = (ctypes.c_int * 3)(4100, 1504, 1504)

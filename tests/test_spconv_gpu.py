@@ -344,3 +344,29 @@ def test_residual_stage_pair_node_matches_module_chain(dev, monkeypatch):
     for a, b in zip(res["1"], res["0"]):
         scale = float(b.abs().max().clamp_min(1e-6))
         assert float((a - b).abs().max()) <= 2e-5 * scale + 1e-7, (a.shape, float((a - b).abs().max()), scale)
+
+
+@pytest.mark.parametrize("m_in,m_out,subm", [(100, 0, False), (0, 16, False), (0, 0, True)])
+def test_empty_tables(dev, m_in, m_out, subm):
+    """A convolution with no output rows (forward) or no input rows (data gradient) gives an empty tensor, and its weight
+    gradient is zero, without an error and without a tile plan being read: hand-built rulebooks (no geometry kernel),
+    a strided table without outputs, a strided table whose 16 outputs have no input, an empty submanifold table."""
+    from efg_amd import _lib
+    from efg_amd.spconv import core
+
+    cin, cout, kvol = 16, 32, 27
+    rb = core.Rulebook(torch.full((kvol, m_out), -1, dtype=torch.int32, device=dev), m_in, m_out, kvol, subm)
+    g = torch.Generator().manual_seed(m_in + m_out)
+    w = torch.randn(cout, kvol, cin, generator=g).to(dev)
+    feats, go = torch.randn(m_in, cin, generator=g).to(dev), torch.randn(m_out, cout, generator=g).to(dev)
+    err = _lib.lib().efg_last_error()
+    if m_out == 0:
+        out = core._conv_forward(feats, w, None, rb)
+        assert tuple(out.shape) == (0, cout) and out.dtype == torch.float32
+    if m_in == 0:
+        grad_in = core._conv_dgrad(go, w, rb)
+        assert tuple(grad_in.shape) == (0, cin) and grad_in.dtype == torch.float32
+    grad_w = core._conv_wgrad(feats, go, rb)
+    torch.cuda.synchronize()
+    assert tuple(grad_w.shape) == (cout, kvol, cin) and not bool(grad_w.any())
+    assert _lib.lib().efg_last_error() == err
