@@ -28,9 +28,12 @@
 //                  occupied cells are compacted into a voxel list, then one thread per voxel takes the max_points
 //                  lowest point indices in order, looks its voxel id up in the bitmap prefix (rank of its first point)
 //                  and writes rows, zero padding, coordinates, count and the fused mean.
-// 6 kernels + 1 clear kernel (counters, chunk totals, look-back records) per call.  All scenes of a batch go through one launch per
-// stage (blockIdx.y = scene).  K4 / K5 run a fixed grid whose workgroups loop over the work lists (a launch sized for
-// the worst case -- 19k workgroups, 5 % of them with work -- spent 20 us on dispatching the empty ones).
+// 6 launches per call (K1 K2 K3 K4 K4b K5; K3 / K4 / K5 are skipped for an empty cloud): the words that must be zero
+// when a call starts live in a self-cleaning buffer the library owns per stream (see VoxState).  Only under stream
+// capture does a seventh launch, vox_fill_kernel, clear them in the caller's workspace.  All scenes of a batch go
+// through one launch per stage (blockIdx.y = scene).  K4 / K5 run a fixed grid whose workgroups loop over the work
+// lists (a launch sized for the worst case -- 19k workgroups, 5 % of them with work -- spent 20 us on dispatching the
+// empty ones).
 #include "voxelize_common.h"
 
 #include <map>
@@ -125,15 +128,6 @@ __device__ __forceinline__ int stage_rows(const float* __restrict__ pts, long lo
 
 // K1 ------------------------------------------------------------------------------------------------------------
 // pos[i] = xcd << 28 | place of point i inside its (supercell, xcd) group; kNone for points outside the range.
-// counters, chunk totals and look-back records of a call: cleared words
-__global__ void __launch_bounds__(256) vox_clear_kernel(unsigned* __restrict__ p, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x; i < n; i += (size_t)gridDim.x * 1024) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (i + u * 256 < n) p[i + u * 256] = 0u;
-  }
-}
-
 template <bool STAGE>
 __global__ void __launch_bounds__(256)
 vox_bin_count_kernel(const float* __restrict__ pts, SceneOffsets so, SceneWords sw, int f, VoxGeom g, BinGeom bg,
@@ -217,6 +211,23 @@ vox_bin_count_kernel(const float* __restrict__ pts, SceneOffsets so, SceneWords 
   mark(dbg, 0, 3);   // group atomics returned, places written
 }
 
+// Decoupled look-back of the two scans (K2, K4b): the record a lower-indexed workgroup publishes, 0 until then.  A
+// workgroup only waits for workgroups with a LOWER index, which are dispatched before it and publish without waiting
+// for anybody -- the wait always ends.  Bounded all the same: a broken invariant should fail a test, not hang the
+// device.  A record that never came would make the prefix silently wrong: the error word is set and K4b turns it into
+// voxel_num = -1.
+template <typename T>
+__device__ __forceinline__ T lookback_wait(const T* rec, unsigned* err) {
+  T x = 0;
+  for (int polls = 0; polls < (1 << 22); ++polls) {
+    x = __hip_atomic_load(rec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (x) break;
+    __builtin_amdgcn_s_sleep(2);
+  }
+  if (!x) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return x;
+}
+
 // K2 ------------------------------------------------------------------------------------------------------------
 // part[chunk] = 1 << 63 | chunk's points << 30 | big bins << 15 | small bins; 0 = not published yet.
 __global__ void __launch_bounds__(256)
@@ -264,21 +275,12 @@ vox_bin_scan_kernel(SceneOffsets so, BinGeom bg, unsigned* __restrict__ count, u
     __hip_atomic_store(part_s + chunk, (1ull << 63) | ((unsigned long long)(unsigned)csum << 30) | (unsigned)clist,
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   mark(dbg, 1, 1);   // chunk reduced + published
-  // Decoupled look-back: the totals of the chunks before this one.  A workgroup only waits for workgroups with a LOWER
-  // index, which are dispatched before it and publish without waiting for anybody -- the wait always ends.  (Bounded
-  // all the same: a broken invariant should fail a test, not hang the device.)  The three fields are summed separately:
-  // a scene may hold more than 2^15 small bins.
+  // the totals of the chunks before this one; the three fields are summed separately: a scene may hold more than 2^15
+  // small bins
   unsigned long long a_pts = 0;
   unsigned a_s = 0, a_b = 0;
   for (int c = tid; c < chunk; c += 256) {
-    unsigned long long x = 0;
-    for (int polls = 0; polls < (1 << 22); ++polls) {
-      x = __hip_atomic_load(part_s + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (x) break;
-      __builtin_amdgcn_s_sleep(2);
-    }
-    // a chunk that never published: the prefix below would be silently wrong -- K4b turns the flag into voxel_num = -1
-    if (!x) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long x = lookback_wait(part_s + c, err);
     a_pts += (x >> 30) & 0x1ffffffffull;
     a_s += (unsigned)x & 0x7fffu;
     a_b += ((unsigned)x >> 15) & 0x7fffu;
@@ -406,10 +408,26 @@ __device__ __forceinline__ unsigned lds_slot(unsigned* keys, unsigned t, unsigne
   }
 }
 
-__device__ __forceinline__ unsigned small_table_size(unsigned p) {
-  unsigned t = 64;
-  while (t < 2 * p) t <<= 1;
-  return t;  // <= kSmallT for p <= kSmall
+// A wave's small bin in K4 / K5: its record {supercell, first place, points} (all 0 past the end of the list) and its
+// two-array LDS table of t slots, emptied (key = kNone, val = val0).  The caller's __syncthreads() follows.
+struct SmallBin {
+  unsigned sc, b, p, t;
+};
+__device__ __forceinline__ SmallBin small_bin_setup(const uint4* __restrict__ small_s, unsigned bin, unsigned nsmall,
+                                                    int lane, unsigned* key, unsigned* val, unsigned val0) {
+  SmallBin s = {0u, 0u, 0u, 64u};
+  if (bin < nsmall) {
+    const uint4 rec = small_s[bin];
+    s.sc = rec.x;
+    s.b = rec.y;
+    s.p = rec.z;
+  }
+  while (s.t < 2 * s.p) s.t <<= 1;   // <= kSmallT for p <= kSmall
+  for (unsigned i = lane; i < s.t; i += 64) {
+    key[i] = kNone;
+    val[i] = val0;
+  }
+  return s;
 }
 
 // K4 ------------------------------------------------------------------------------------------------------------
@@ -453,20 +471,10 @@ vox_first_kernel(SceneOffsets so, SceneWords sw, BinGeom bg, const uint4* __rest
       }
       __syncthreads();
     } else {
-      const unsigned bin = (item - nbig) * 4 + wave;
       unsigned* key = tab + wave * (2 * kSmallT);
       unsigned* val = key + kSmallT;
-      unsigned p = 0, b = 0;
-      if (bin < nsmall) {
-        const uint4 rec = small_list[sbase + bin];
-        p = rec.z;
-        b = rec.y;
-      }
-      const unsigned t = small_table_size(p);
-      for (unsigned s = lane; s < t; s += 64) {
-        key[s] = kNone;
-        val[s] = kNone;
-      }
+      const SmallBin sb = small_bin_setup(small_list + sbase, (item - nbig) * 4 + wave, nsmall, lane, key, val, kNone);
+      const unsigned p = sb.p, b = sb.b, t = sb.t;
       __syncthreads();
       uint2 m[4];
 #pragma unroll
@@ -516,16 +524,7 @@ vox_rank_kernel(SceneOffsets so, SceneWords sw, const unsigned char* __restrict_
   unsigned* part_s = part2 + (size_t)scene * nchunks2;
   if (tid == 0) __hip_atomic_store(part_s + chunk, 0x80000000u | (unsigned)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   unsigned acc = 0;
-  for (int cc = tid; cc < chunk; cc += 256) {   // look-back: lower-indexed workgroups publish without waiting (see K2)
-    unsigned x = 0;
-    for (int polls = 0; polls < (1 << 22); ++polls) {
-      x = __hip_atomic_load(part_s + cc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (x) break;
-      __builtin_amdgcn_s_sleep(2);
-    }
-    if (!x) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (see K2)
-    acc += x & 0x7fffffffu;
-  }
+  for (int cc = tid; cc < chunk; cc += 256) acc += lookback_wait(part_s + cc, err) & 0x7fffffffu;
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, 64);
   if ((tid & 63) == 0) s_w[tid >> 6] = acc;
@@ -552,7 +551,7 @@ vox_rank_kernel(SceneOffsets so, SceneWords sw, const unsigned char* __restrict_
   mark(dbg, 5, 1);
 }
 
-// One voxel: the cell's points are seg_idx[start .. start + n) (point indices) / seg_e (their places in the bin).
+// what K5 needs to write a voxel of its scene
 struct WriteArgs {
   const float* rows;
   const unsigned* bits_s;
@@ -565,17 +564,6 @@ struct WriteArgs {
   unsigned beg;
 };
 
-__device__ __forceinline__ void voxel_coords(const WriteArgs& a, const BinGeom& bg, unsigned sc, unsigned lc, long long vid,
-                                             int kept) {
-  const int bx = sc % bg.nsx, by = (sc / bg.nsx) % bg.nsy, bz = sc / (bg.nsx * bg.nsy);
-  int* c = a.coors + vid * a.coors_cols;
-  if (a.coors_cols == 4) *c++ = a.scene;
-  c[0] = bz * bg.sz + (int)(lc >> (2 * kSB));
-  c[1] = by * kSXY + (int)((lc >> kSB) & (kSXY - 1));
-  c[2] = bx * kSXY + (int)(lc & (kSXY - 1));
-  a.npv[vid] = kept;
-}
-
 // 16-byte stores at 4-byte alignment (a voxel's block starts at vid * max_points * f floats): gfx950 global memory
 // takes unaligned dwordx4 accesses; the packed type makes the compiler emit them.
 struct __attribute__((packed, aligned(4))) f4u {
@@ -585,17 +573,18 @@ struct __attribute__((packed, aligned(4))) i4u {
   int x, y, z, w;
 };
 
-// The common shapes (max_points == KMAX, f == F, both compile-time: ConQueR / Voxel-DETR 5 x 5, CenterPoint 4-sweep
-// 5 x 6) written with 16-byte stores: 7 + 2 + 1 store instructions per voxel instead of 25 + 5 + 4 four-byte ones.
-// A lane's scattered store costs the address pipeline one cache line whatever its width; with the four-byte stores the
-// output stores were a third of the kernel (a build without them: 39 -> 27 us).
-template <int KMAX, int F>
-__device__ __forceinline__ void emit_voxel_static(const WriteArgs& a, const BinGeom& bg, unsigned sc, unsigned lc,
-                                                  unsigned bin_base, const unsigned* seg_idx, const unsigned* seg_e,
-                                                  unsigned start, unsigned n) {
-  static_assert(F >= 4 && F <= 8, "row = one or two 16-byte pieces");
-  const int kept = (int)min(n, (unsigned)KMAX);
-  unsigned bi[KMAX], be[KMAX];
+// The pieces of one voxel, each written once --------------------------------------------------------------------
+// The KMAX lowest point indices of the segment (idx, ascending; kNone past its end) and their places in the bin, by
+// streaming insertion into a sorted register array: one pass over the segment.
+template <int KMAX>
+struct Lowest {
+  unsigned idx[KMAX], place[KMAX];
+};
+template <int KMAX>
+__device__ __forceinline__ Lowest<KMAX> select_lowest(const unsigned* seg_idx, const unsigned* seg_e, unsigned start,
+                                                      unsigned n) {
+  Lowest<KMAX> low;
+  unsigned(&bi)[KMAX] = low.idx, (&be)[KMAX] = low.place;
 #pragma unroll
   for (int s = 0; s < KMAX; ++s) {
     bi[s] = kNone;
@@ -614,31 +603,66 @@ __device__ __forceinline__ void emit_voxel_static(const WriteArgs& a, const BinG
       e = te;
     }
   }
-  const unsigned jf = bi[0] - a.beg;
+  return low;
+}
+
+// voxel id = number of first points of the scene before this voxel's first point
+__device__ __forceinline__ long long voxel_id(const WriteArgs& a, unsigned first) {
+  const unsigned jf = first - a.beg;
   const unsigned pw = a.prefix_s[jf >> 5], bw = a.bits_s[jf >> 5];
-  float4 r0[KMAX], r1[KMAX];
+  return a.out_base + (long long)(pw + __popc(bw & ((1u << (jf & 31)) - 1u)));
+}
+
+// (supercell, cell inside it) -> the voxel's coordinate row (z, y, x behind the scene column, if any) and its count;
+// PACKED: the four-column row as one 16-byte store
+template <bool PACKED>
+__device__ __forceinline__ void voxel_coords(const WriteArgs& a, const BinGeom& bg, unsigned sc, unsigned lc, long long vid,
+                                             int kept) {
+  const int bx = sc % bg.nsx, by = (sc / bg.nsx) % bg.nsy, bz = sc / (bg.nsx * bg.nsy);
+  const int cz = bz * bg.sz + (int)(lc >> (2 * kSB)), cy = by * kSXY + (int)((lc >> kSB) & (kSXY - 1)),
+            cx = bx * kSXY + (int)(lc & (kSXY - 1));
+  int* c = a.coors + vid * a.coors_cols;
+  if (PACKED && a.coors_cols == 4) {
+    i4u c4;
+    c4.x = a.scene, c4.y = cz, c4.z = cy, c4.w = cx;
+    *reinterpret_cast<i4u*>(c) = c4;
+  } else {
+    if (a.coors_cols == 4) *c++ = a.scene;
+    c[0] = cz, c[1] = cy, c[2] = cx;
+  }
+  a.npv[vid] = kept;
+}
+
+// ALL row loads of the voxel (up to KMAX 32-byte rows of rs floats; rows past `kept` re-read row 0) issued together and
+// branch-free, so the voxel costs ONE memory round trip before its stores (loads inside `if (k < kept)` were waited
+// for one row at a time: five round trips per voxel).
+template <int KMAX>
+struct Rows {
+  float4 lo[KMAX], hi[KMAX];   // features 0-3 and 4-7 of every slot
+  __device__ __forceinline__ float at(int k, int t) const {   // (k, t compile-time after unrolling)
+    const float4& q = t < 4 ? lo[k] : hi[k];
+    return (t & 3) == 0 ? q.x : (t & 3) == 1 ? q.y : (t & 3) == 2 ? q.z : q.w;
+  }
+};
+template <int KMAX>
+__device__ __forceinline__ Rows<KMAX> gather_rows(const float* rows, unsigned bin_base, const Lowest<KMAX>& low, int kept,
+                                                  int rs) {
+  Rows<KMAX> r;
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) {
-    const float4* r = reinterpret_cast<const float4*>(a.rows + ((size_t)bin_base + be[k < kept ? k : 0]) * 8);   // rs == 8
-    r0[k] = r[0];
-    r1[k] = F > 4 ? r[1] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float4* p = reinterpret_cast<const float4*>(rows + ((size_t)bin_base + low.place[k < kept ? k : 0]) * rs);
+    r.lo[k] = p[0];
+    r.hi[k] = rs > 4 ? p[1] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   }
-  const long long vid = a.out_base + (long long)(pw + __popc(bw & ((1u << (jf & 31)) - 1u)));
-  // coordinates / count
-  {
-    const int bx = sc % bg.nsx, by = (sc / bg.nsx) % bg.nsy, bz = sc / (bg.nsx * bg.nsy);
-    const int cz = bz * bg.sz + (int)(lc >> (2 * kSB)), cy = by * kSXY + (int)((lc >> kSB) & (kSXY - 1)),
-              cx = bx * kSXY + (int)(lc & (kSXY - 1));
-    if (a.coors_cols == 4) {
-      i4u c4;
-      c4.x = a.scene, c4.y = cz, c4.z = cy, c4.w = cx;
-      *reinterpret_cast<i4u*>(a.coors + vid * 4) = c4;
-    } else {
-      int* c = a.coors + vid * 3;
-      c[0] = cz, c[1] = cy, c[2] = cx;
-    }
-    a.npv[vid] = kept;
-  }
+  return r;
+}
+
+// Store back-end of the common shapes (max_points == KMAX, f == F, both compile-time: ConQueR / Voxel-DETR 5 x 5,
+// CenterPoint 4-sweep 5 x 6), 16-byte stores: 7 + 2 + 1 store instructions per voxel instead of 25 + 5 + 4 four-byte
+// ones.  A lane's scattered store costs the address pipeline one cache line whatever its width; with the four-byte
+// stores the output stores were a third of the kernel (a build without them: 39 -> 27 us).
+template <int KMAX, int F>
+__device__ __forceinline__ void store_voxel_static(const WriteArgs& a, long long vid, int kept, const Rows<KMAX>& r) {
   // the voxel's KMAX x F block, flat, rows past `kept` zero
   float flat[KMAX * F];
   float acc[F];
@@ -646,25 +670,22 @@ __device__ __forceinline__ void emit_voxel_static(const WriteArgs& a, const BinG
   for (int t = 0; t < F; ++t) acc[t] = 0.0f;
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) {
-    const float rv[8] = {r0[k].x, r0[k].y, r0[k].z, r0[k].w, r1[k].x, r1[k].y, r1[k].z, r1[k].w};
 #pragma unroll
     for (int t = 0; t < F; ++t) {
-      const float v = k < kept ? rv[t] : 0.0f;
+      const float v = k < kept ? r.at(k, t) : 0.0f;
       flat[k * F + t] = v;
       acc[t] = __fadd_rn(acc[t], v);   // slot order, like the reader's sum(dim=1); + 0.0f past `kept` changes nothing
     }
   }
-  {
-    float* o = a.voxels + vid * (KMAX * F);
+  float* o = a.voxels + vid * (KMAX * F);
 #pragma unroll
-    for (int q = 0; q + 4 <= KMAX * F; q += 4) {
-      f4u v4;
-      v4.x = flat[q], v4.y = flat[q + 1], v4.z = flat[q + 2], v4.w = flat[q + 3];
-      *reinterpret_cast<f4u*>(o + q) = v4;
-    }
-#pragma unroll
-    for (int q = (KMAX * F) & ~3; q < KMAX * F; ++q) o[q] = flat[q];
+  for (int q = 0; q + 4 <= KMAX * F; q += 4) {
+    f4u v4;
+    v4.x = flat[q], v4.y = flat[q + 1], v4.z = flat[q + 2], v4.w = flat[q + 3];
+    *reinterpret_cast<f4u*>(o + q) = v4;
   }
+#pragma unroll
+  for (int q = (KMAX * F) & ~3; q < KMAX * F; ++q) o[q] = flat[q];
   if (a.mean) {
     float* mo = a.mean + vid * F;
     const float d = (float)kept;
@@ -676,78 +697,51 @@ __device__ __forceinline__ void emit_voxel_static(const WriteArgs& a, const BinG
   }
 }
 
-// FAST (KMAX = 5 or 8 >= max_points, f <= 8: every configuration of the reference's playground): the max_points lowest point
-// indices of the cell by streaming insertion into a sorted register array -- one pass over the segment -- then ALL
-// global loads of the voxel (bitmap word, prefix word, up to eight 32-byte rows; rows past `kept` re-read row 0) issued
-// together and branch-free, so the voxel costs ONE memory round trip before its stores (loads inside `if (k < kept)`
-// were waited for one row at a time: five round trips per voxel).  The mean comes from registers.
-// Generic: selection by repeated minimum (O(n * kept) dependent loads), rows and mean through memory.
-template <int KMAX>   // 0: generic path; 5 / 8: FAST with max_points <= KMAX
+// Store back-end for run-time max_points <= KMAX and f <= 8: four-byte stores, the mean from registers.
+template <int KMAX>
+__device__ __forceinline__ void store_voxel_dynamic(const WriteArgs& a, long long vid, int kept, const Rows<KMAX>& r) {
+  float acc[8];
+#pragma unroll
+  for (int t = 0; t < 8; ++t) acc[t] = 0.0f;
+  float* o = a.voxels + vid * a.max_points * a.f;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) {
+    if (k < kept) {
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        if (t < a.f) {
+          o[k * a.f + t] = r.at(k, t);
+          acc[t] = __fadd_rn(acc[t], r.at(k, t));   // slot order, like the reader's sum(dim=1)
+        }
+      }
+    }
+  }
+  for (int k = kept * a.f; k < a.max_points * a.f; ++k) o[k] = 0.0f;
+  if (a.mean) {
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+      if (t < a.f) a.mean[vid * a.f + t] = __fdiv_rn(acc[t], (float)kept);
+  }
+}
+
+// One voxel: the cell's points are seg_idx[start .. start + n) (point indices) / seg_e (their places in the bin).
+// KMAX = 5 or 8 >= max_points, f <= 8 (every configuration of the reference's playground): selection in one pass,
+// bitmap word, prefix word and rows in one round trip, then one of the two store back-ends (F > 0: max_points == KMAX
+// and f == F exactly).  KMAX == 0, any size: selection by repeated minimum (O(n * kept) dependent loads), rows and
+// mean through memory.
+template <int KMAX, int F>
 __device__ __forceinline__ void emit_voxel(const WriteArgs& a, const BinGeom& bg, unsigned sc, unsigned lc,
                                            unsigned bin_base, const unsigned* seg_idx, const unsigned* seg_e,
                                            unsigned start, unsigned n) {
-  const int kept = (int)min(n, (unsigned)a.max_points);
+  static_assert(F == 0 || (KMAX > 0 && F > 4 && F <= 8), "static rows are two 16-byte pieces (rs == 8)");
+  const int kept = (int)min(n, (unsigned)(F > 0 ? KMAX : a.max_points));
   if constexpr (KMAX > 0) {
-    unsigned bi[KMAX], be[KMAX];
-#pragma unroll
-    for (int s = 0; s < KMAX; ++s) {
-      bi[s] = kNone;
-      be[s] = 0u;
-    }
-#pragma unroll 4
-    for (unsigned j = start; j < start + n; ++j) {
-      unsigned v = seg_idx[j], e = seg_e[j];
-#pragma unroll
-      for (int s = 0; s < KMAX; ++s) {
-        const bool lt = v < bi[s];
-        const unsigned tv = lt ? bi[s] : v, te = lt ? be[s] : e;
-        bi[s] = lt ? v : bi[s];
-        be[s] = lt ? e : be[s];
-        v = tv;
-        e = te;
-      }
-    }
-    const unsigned jf = bi[0] - a.beg;
-    const unsigned pw = a.prefix_s[jf >> 5], bw = a.bits_s[jf >> 5];
-    float4 r0[KMAX], r1[KMAX];
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      const float4* r = reinterpret_cast<const float4*>(a.rows + ((size_t)bin_base + be[k < kept ? k : 0]) * a.rs);
-      r0[k] = r[0];
-      r1[k] = a.rs > 4 ? r[1] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-    // voxel id = number of first points of the scene before this voxel's first point
-    const long long vid = a.out_base + (long long)(pw + __popc(bw & ((1u << (jf & 31)) - 1u)));
-    voxel_coords(a, bg, sc, lc, vid, kept);
-    float acc[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) acc[t] = 0.0f;
-    float* o = a.voxels + vid * a.max_points * a.f;
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k) {
-      if (k < kept) {
-#define EFG_VOX_PUT(t, val)                  \
-  if (t < a.f) {                             \
-    o[k * a.f + t] = val;                    \
-    acc[t] = __fadd_rn(acc[t], val); /* slot order, like the reader's sum(dim=1) */ \
-  }
-        EFG_VOX_PUT(0, r0[k].x)
-        EFG_VOX_PUT(1, r0[k].y)
-        EFG_VOX_PUT(2, r0[k].z)
-        EFG_VOX_PUT(3, r0[k].w)
-        EFG_VOX_PUT(4, r1[k].x)
-        EFG_VOX_PUT(5, r1[k].y)
-        EFG_VOX_PUT(6, r1[k].z)
-        EFG_VOX_PUT(7, r1[k].w)
-#undef EFG_VOX_PUT
-      }
-    }
-    for (int k = kept * a.f; k < a.max_points * a.f; ++k) o[k] = 0.0f;
-    if (a.mean) {
-#pragma unroll
-      for (int t = 0; t < 8; ++t)
-        if (t < a.f) a.mean[vid * a.f + t] = __fdiv_rn(acc[t], (float)kept);
-    }
+    const Lowest<KMAX> low = select_lowest<KMAX>(seg_idx, seg_e, start, n);
+    const long long vid = voxel_id(a, low.idx[0]);
+    const Rows<KMAX> r = gather_rows<KMAX>(a.rows, bin_base, low, kept, F > 0 ? 8 : a.rs);
+    voxel_coords<(F > 0)>(a, bg, sc, lc, vid, kept);
+    if constexpr (F > 0) store_voxel_static<KMAX, F>(a, vid, kept, r);
+    else store_voxel_dynamic<KMAX>(a, vid, kept, r);
   } else {
     long long vid = 0;
     unsigned prev = 0;
@@ -762,9 +756,8 @@ __device__ __forceinline__ void emit_voxel(const WriteArgs& a, const BinGeom& bg
       }
       prev = best;
       if (k == 0) {
-        const unsigned jf = best - a.beg;
-        vid = a.out_base + (long long)(a.prefix_s[jf >> 5] + __popc(a.bits_s[jf >> 5] & ((1u << (jf & 31)) - 1u)));
-        voxel_coords(a, bg, sc, lc, vid, kept);
+        vid = voxel_id(a, best);
+        voxel_coords<false>(a, bg, sc, lc, vid, kept);
       }
       const float* r = a.rows + ((size_t)bin_base + be) * a.rs;
       float* o = a.voxels + (vid * a.max_points + k) * a.f;
@@ -842,24 +835,33 @@ vox_write_kernel(SceneOffsets so, SceneWords sw, BinGeom bg, int f, int rs, cons
       const unsigned pval = parts == 4 ? ((part & 1u) | ((part >> 1) << kSB)) : part;
       for (int c = tid; c < bg.cells; c += 256) tab[c] = 0u;
       __syncthreads();
-      const bool in_reg = p <= 4 * 256;   // the bin's points stay in registers between the count and the scatter pass
+      // Two passes (count, scatter) over this workgroup's share of the bin's records, each as fn(record, place in the
+      // bin).  A bin of up to 1024 points keeps its records in registers between the passes, a larger one reads them
+      // again.
+      const bool in_reg = p <= 4 * 256;
       uint2 mr[4];
-      if (in_reg) {
+      const auto load4 = [&](unsigned e0, uint2(&m)[4]) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) mr[j] = tid + 256 * j < p ? meta[b + tid + 256 * j] : make_uint2(kNone, 0u);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (mr[j].x < ib && (mr[j].y & pmask) == pval) atomicAdd(&tab[mr[j].y], 1u);   // (kNone >= ib always)
-      } else {
-        for (unsigned e0 = tid; e0 < p; e0 += 1024) {
-          uint2 m[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) m[j] = e0 + 256 * j < p ? meta[b + e0 + 256 * j] : make_uint2(kNone, 0u);
+        for (int j = 0; j < 4; ++j) m[j] = e0 + 256 * j < p ? meta[b + e0 + 256 * j] : make_uint2(kNone, 0u);
+      };
+      const auto for_my_records = [&](auto fn) {
+        const auto apply4 = [&](unsigned e0, const uint2(&m)[4]) {
 #pragma unroll
           for (int j = 0; j < 4; ++j)
-            if (m[j].x < ib && (m[j].y & pmask) == pval) atomicAdd(&tab[m[j].y], 1u);
+            if (m[j].x < ib && (m[j].y & pmask) == pval) fn(m[j], e0 + 256 * j);   // (kNone >= ib always)
+        };
+        if (in_reg) {
+          apply4(tid, mr);
+        } else {
+          for (unsigned e0 = tid; e0 < p; e0 += 1024) {
+            uint2 m[4];
+            load4(e0, m);
+            apply4(e0, m);
+          }
         }
-      }
+      };
+      if (in_reg) load4(tid, mr);
+      for_my_records([&](const uint2& m, unsigned) { atomicAdd(&tab[m.y], 1u); });
       __syncthreads();
       int nvox, tot;
       {  // exclusive scan over the cells in place (thread t owns cells [t * per, (t + 1) * per)) and, in the same pass,
@@ -884,59 +886,28 @@ vox_write_kernel(SceneOffsets so, SceneWords sw, BinGeom bg, int f, int rs, cons
       const bool in_lds = tot <= kSegLds;   // (this workgroup's share of the bin)
       unsigned* si = in_lds ? seg_lds : seg_idx_g + (size_t)part * seg_stride + b;
       unsigned* se = in_lds ? seg_lds + kSegLds : seg_e_g + (size_t)part * seg_stride + b;
-      if (in_reg) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (mr[j].x < ib && (mr[j].y & pmask) == pval) {
-            const unsigned q = atomicAdd(&tab[mr[j].y], 1u);  // afterwards tab[c] = END of cell c = start of cell c + 1
-            si[q] = mr[j].x;
-            se[q] = tid + 256 * j;
-          }
-        }
-      } else {
-        for (unsigned e0 = tid; e0 < p; e0 += 1024) {
-          uint2 m[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) m[j] = e0 + 256 * j < p ? meta[b + e0 + 256 * j] : make_uint2(kNone, 0u);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (m[j].x < ib && (m[j].y & pmask) == pval) {
-              const unsigned q = atomicAdd(&tab[m[j].y], 1u);
-              si[q] = m[j].x;
-              se[q] = e0 + 256 * j;
-            }
-          }
-        }
-      }
+      for_my_records([&](const uint2& m, unsigned e) {
+        const unsigned q = atomicAdd(&tab[m.y], 1u);  // afterwards tab[c] = END of cell c = start of cell c + 1
+        si[q] = m.x;
+        se[q] = e;
+      });
       __syncthreads();
       mark(dbg, 4, 1);   // sorted by cell
       for (int v = tid; v < nvox; v += 256) {
         const unsigned c = vlist[v];
         const unsigned en = tab[c], st = c ? tab[c - 1] : 0u;
-        if constexpr (F > 0) emit_voxel_static<KMAX, F>(a, bg, sc, c, b, si, se, st, en - st);
-        else emit_voxel<KMAX>(a, bg, sc, c, b, si, se, st, en - st);
+        emit_voxel<KMAX, F>(a, bg, sc, c, b, si, se, st, en - st);
       }
       __syncthreads();
       mark(dbg, 4, 2);   // big bin written
     } else {
-      const unsigned bin = (item - nbig) * 4 + wave;
       unsigned* key = tab + wave * kSmallLds;
       unsigned* off = key + kSmallT;
       unsigned* si = off + kSmallT;
       unsigned* se = si + kSmall;
       unsigned* vlist = se + kSmall;
-      unsigned p = 0, b = 0, sc = 0;
-      if (bin < nsmall) {
-        const uint4 rec = small_list[sbase + bin];
-        sc = rec.x;
-        p = rec.z;
-        b = rec.y;
-      }
-      const unsigned t = small_table_size(p);
-      for (unsigned s = lane; s < t; s += 64) {
-        key[s] = kNone;
-        off[s] = 0u;
-      }
+      const SmallBin sb = small_bin_setup(small_list + sbase, (item - nbig) * 4 + wave, nsmall, lane, key, off, 0u);
+      const unsigned sc = sb.sc, p = sb.p, b = sb.b, t = sb.t;
       __syncthreads();
       uint2 m[4];
       unsigned sl[4];
@@ -985,8 +956,7 @@ vox_write_kernel(SceneOffsets so, SceneWords sw, BinGeom bg, int f, int rs, cons
       for (int v = lane; v < nvox; v += 64) {
         const unsigned s = vlist[v];
         const unsigned en = off[s], st = s ? off[s - 1] : 0u;
-        if constexpr (F > 0) emit_voxel_static<KMAX, F>(a, bg, sc, key[s], b, si, se, st, en - st);
-        else emit_voxel<KMAX>(a, bg, sc, key[s], b, si, se, st, en - st);
+        emit_voxel<KMAX, F>(a, bg, sc, key[s], b, si, se, st, en - st);
       }
       __syncthreads();
       mark(dbg, 4, 4);   // small bins written
@@ -1022,20 +992,39 @@ bool bins_layout(int64_t n_total, int batch, int f, const VoxGeom& g, BinsLayout
 // more words than it holds (both synchronise: once per process and size); a call that fails between its launches leaves the
 // buffer marked dirty and the next call zeroes it with one asynchronous memset.  Calls on ONE
 // stream are issued by one thread at a time (as for stream-K, include/efg_hip.h).  While the stream is being CAPTURED into a HIP
-// graph the call takes its cleared words from the caller's workspace and clears them with vox_clear_kernel, as before (a
+// graph the call takes its cleared words from the caller's workspace and clears them with vox_fill_kernel, as before (a
 // replay must not depend on what eager calls left behind, and the first-use allocation would invalidate the capture).
 constexpr size_t kOwnRecordWords = 49152;   // >= the records of any call the binned path takes (<= 2^22 supercells, < 2^28 points)
 struct VoxState {
   unsigned* words = nullptr;
   size_t cap = 0;
-  bool dirty = true;
+  bool dirty = true;   // the words may be non-zero: the next call zeroes them first
+  int in_flight = 0;   // calls that hold a pointer to this entry (between vox_state_for_stream and ~VoxHold)
 };
 std::mutex g_vox_mu;
 std::map<std::pair<int, hipStream_t>, VoxState> g_vox_pool;
 
-constexpr size_t kVoxPoolMax = 32;   // (device, stream) entries kept; a process that keeps creating streams recycles them
+// (device, stream) entries kept; a process that keeps creating streams recycles the idle ones -- the map passes this
+// size only while every entry is held by a call
+constexpr size_t kVoxPoolMax = 32;
 
-int vox_state_for_stream(hipStream_t stream, size_t words, VoxState** out) {
+// A call's hold on its stream's state, given back on every way out of the call.  `clean`: every launch of the call is
+// queued, so the counters are zero again when K2 has run; a call that failed in between leaves the words dirty.
+struct VoxHold {
+  VoxState* st = nullptr;
+  bool clean = false;
+  VoxHold() = default;
+  VoxHold(const VoxHold&) = delete;
+  VoxHold& operator=(const VoxHold&) = delete;
+  ~VoxHold() {
+    if (!st) return;
+    std::lock_guard<std::mutex> lock(g_vox_mu);
+    --st->in_flight;
+    if (clean) st->dirty = false;
+  }
+};
+
+int vox_state_for_stream(hipStream_t stream, size_t words, VoxHold* hold) {
   int dev = 0;
   EFG_HIP_TRY(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lock(g_vox_mu);
@@ -1053,10 +1042,15 @@ int vox_state_for_stream(hipStream_t stream, size_t words, VoxState** out) {
     }
   } relaxed;
   if (!g_vox_pool.count(key) && g_vox_pool.size() >= kVoxPoolMax) {
-    // streams that were destroyed (or are simply many): drop every other entry (hipFree synchronises, so no launch still
-    // reads a buffer that goes); a stream handle that is reused later starts from a fresh, zeroed buffer
+    // streams that were destroyed (or are simply many): drop every idle entry (hipFree synchronises, so no launch still
+    // reads a buffer that goes); a stream handle that is reused later starts from a fresh, zeroed buffer.  An entry
+    // whose call is still between its launches on another thread stays: that thread holds a pointer to it.
     relaxed.enter();
     for (auto it = g_vox_pool.begin(); it != g_vox_pool.end();) {
+      if (it->second.in_flight > 0) {
+        ++it;
+        continue;
+      }
       if (it->second.words) (void)hipFree(it->second.words);
       it = g_vox_pool.erase(it);
     }
@@ -1073,14 +1067,54 @@ int vox_state_for_stream(hipStream_t stream, size_t words, VoxState** out) {
     st.dirty = true;
   }
   if (st.dirty) EFG_HIP_TRY(hipMemsetAsync(st.words, 0, st.cap * sizeof(unsigned), stream));
-  st.dirty = true;   // until the call's last launch has been issued (vox_state_done)
-  *out = &st;
+  st.dirty = true;   // until the call's last launch has been issued (VoxHold::clean)
+  ++st.in_flight;
+  hold->st = &st;   // (a map's elements stay where they are when others come and go)
   return EFG_OK;
 }
 
-void vox_state_done(VoxState* st) {   // every launch of the call is queued: the counters are zero again when K2 has run
-  std::lock_guard<std::mutex> lock(g_vox_mu);
-  st->dirty = false;
+// The buffers of a call in workspace order: with a null base nothing is carved and `bytes` is what the call needs.
+struct BinsBuffers {
+  size_t words;           // bitmap words (32 points each; every scene padded to whole 16-byte groups)
+  size_t part2_words;     // look-back records of K4b, >= nchunks2 * batch
+  size_t cleared_words;   // counters, part, part2, error word: zero when the call starts
+  size_t bytes;
+  bool ok;
+  unsigned *count, *basex, *nlist, *pos, *seg_idx, *seg_e, *bits, *prefix;
+  uint4 *small_list, *big_list;
+  uint2* meta;
+  float* rows;
+  unsigned char* flags;
+};
+
+BinsBuffers bins_buffers(const BinsLayout& L, int64_t n_total, int batch, void* base, size_t cap) {
+  BinsBuffers B;
+  B.words = (size_t)(n_total / 32 + 4 * batch + 4);
+  B.part2_words = (size_t)(n_total / 8192 + 2) * batch;
+  B.cleared_words = L.s_total * kXcd + (size_t)L.nchunks * batch * 2 + B.part2_words + 4;
+  Workspace w(base, base ? cap : ~(size_t)0);
+  B.count = w.take<unsigned>(B.cleared_words);   // (the workspace keeps its layout whether or not these words are used)
+  B.basex = w.take<unsigned>(L.s_total * kXcd);
+  B.small_list = w.take<uint4>(L.s_total);                   // 16-byte bin records
+  B.big_list = w.take<uint4>(4 * align_up(L.s_total, 16));   // (up to 4 items per bin)
+  B.nlist = w.take<unsigned>(4 * kMaxBatch);                 // nlist, i_break
+  B.pos = w.take<unsigned>(L.n);
+  B.meta = w.take<uint2>(L.n);
+  B.rows = w.take<float>((size_t)L.n * L.rs);
+  B.seg_idx = w.take<unsigned>(4 * (size_t)L.n);   // bins above kSegLds points: one range per part of a split bin
+  B.seg_e = w.take<unsigned>(4 * (size_t)L.n);
+  B.bits = w.take<unsigned>(B.words);
+  B.prefix = w.take<unsigned>(B.words);
+  B.flags = w.take<unsigned char>(B.words * 32);   // one byte per point
+  B.ok = w.ok;
+  B.bytes = w.off + 256;
+  return B;
+}
+
+// K1 and K3 come in a staged and an in-place form: one argument list for both
+template <typename K, typename... A>
+void launch_staged(bool stage, K staged, K in_place, dim3 grid, size_t lds, hipStream_t stream, A... args) {
+  hipLaunchKernelGGL(stage ? staged : in_place, grid, dim3(256), lds, stream, args...);
 }
 
 }  // namespace
@@ -1091,19 +1125,7 @@ size_t bins_debug_timeline_words() { return (size_t)6 * 8 * kDbgMaxWg; }
 size_t bins_workspace_bytes(int64_t n_total, int batch, int f, const VoxGeom& g) {
   BinsLayout L;
   if (!bins_layout(n_total, batch, f, g, &L)) return 0;
-  const size_t words = (size_t)(n_total / 32 + 4 * batch + 4);
-  size_t b = 0;
-  b += align_up((L.s_total * kXcd + (size_t)L.nchunks * batch * 2 + ((size_t)(n_total / 8192 + 2) * batch) + 4) * 4, 256);  // count, part, part2, err (cleared)
-  b += align_up(L.s_total * kXcd * 4, 256);                    // basex
-  b += 5 * align_up(L.s_total * 16, 256);                      // small_list, big_list x4 (16-byte bin records)
-  b += align_up(4 * kMaxBatch * 4, 256);                       // nlist, i_break
-  b += align_up((size_t)L.n * 4, 256);                         // pos
-  b += align_up((size_t)L.n * 8, 256);                         // meta
-  b += align_up((size_t)L.n * L.rs * 4, 256);                  // rows
-  b += 2 * align_up((size_t)L.n * 16, 256);                    // seg_idx, seg_e (bins above kSegLds points; x4: parts of split bins)
-  b += 2 * align_up(words * 4, 256);                           // bits, prefix
-  b += align_up(words * 32, 256);                              // flags (one byte per point)
-  return b + 256;
+  return bins_buffers(L, n_total, batch, nullptr, 0).bytes;
 }
 
 int bins_hard_voxelize(const HardArgs& a) {
@@ -1121,80 +1143,51 @@ int bins_hard_voxelize(const HardArgs& a) {
   for (int b = 0; b < batch; ++b)   // every scene's words start on a 16-byte boundary (vector loads of the scan)
     sw.wb[b + 1] = sw.wb[b] + (int)(ceil_div(so.off[b + 1] - so.off[b], 128) * 4);
   for (int b = batch + 1; b <= kMaxBatch; ++b) so.off[b] = so.off[batch];  // off[kMaxBatch] = total rows (stage_rows)
-  const size_t words = (size_t)(a.n_total / 32 + 4 * batch + 4);
-  Workspace w(a.ws, a.ws_bytes);
   int max_words = 0;
   for (int b = 0; b < batch; ++b) max_words = std::max(max_words, sw.wb[b + 1] - sw.wb[b]);
   const int nchunks2 = std::max(1, (int)ceil_div(max_words, 256));   // K4b: 256 words = 8192 points per workgroup
-  const size_t part2_words = (size_t)(a.n_total / 8192 + 2) * batch;   // >= nchunks2 * batch
-  const size_t cleared_words = L.s_total * kXcd + (size_t)L.nchunks * batch * 2 + part2_words + 4;   // (+ the error word)
-  unsigned* count = w.take<unsigned>(cleared_words);   // (the workspace keeps its layout whether or not these words are used)
-  // (8-byte aligned: s_total is a multiple of 4)
-  unsigned long long* part = count ? reinterpret_cast<unsigned long long*>(count + L.s_total * kXcd) : nullptr;
-  unsigned* part2 = count ? count + L.s_total * kXcd + (size_t)L.nchunks * batch * 2 : nullptr;
-  unsigned* err = count ? count + cleared_words - 4 : nullptr;
-  unsigned* basex = w.take<unsigned>(L.s_total * kXcd);
-  uint4* small_list = w.take<uint4>(L.s_total);
-  uint4* big_list = w.take<uint4>(4 * L.s_total);
-  unsigned* nlist = w.take<unsigned>(4 * kMaxBatch);
-  unsigned* i_break = nlist ? nlist + 2 * kMaxBatch : nullptr;
-  unsigned* pos = w.take<unsigned>(L.n);
-  uint2* meta = w.take<uint2>(L.n);
-  float* rows = w.take<float>((size_t)L.n * L.rs);
-  unsigned* seg_idx = w.take<unsigned>(4 * (size_t)L.n);   // (one range per part of a split bin)
-  unsigned* seg_e = w.take<unsigned>(4 * (size_t)L.n);
-  unsigned* bits = w.take<unsigned>(words);
-  unsigned* prefix = w.take<unsigned>(words);
-  unsigned char* flags = w.take<unsigned char>(words * 32);
-  if (!w.ok) {
+  const BinsBuffers B = bins_buffers(L, a.n_total, batch, a.ws, a.ws_bytes);
+  if (!a.ws || !B.ok) {
     set_error("hard_voxelize workspace too small: need %zu bytes, got %zu",
               bins_workspace_bytes(a.n_total, batch, f, a.g), a.ws_bytes);
     return EFG_E_WORKSPACE;
   }
+  // the cleared words [counters | part | part2 | error word] (part is 8-byte aligned: s_total is a multiple of 4)
+  const size_t record_words = B.cleared_words - L.s_total * kXcd;
+  unsigned* count = B.count;
+  unsigned* records = count + L.s_total * kXcd;
+  unsigned* i_break = B.nlist + 2 * kMaxBatch;
   const dim3 blk(256);
-  // the cleared words: the library's own, self-cleaning buffer of this stream (see VoxState) unless the stream is being captured
-  VoxState* own = nullptr;
+  // ... in the library's own, self-cleaning buffer of this stream (see VoxState) unless the stream is being captured
+  VoxHold own;
   {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (stream) (void)hipStreamIsCapturing(stream, &cap);
-    const size_t record_words = cleared_words - L.s_total * kXcd;
     if (cap == hipStreamCaptureStatusNone && record_words <= kOwnRecordWords) {
       // [records: kOwnRecordWords, zeroed by K1 of the call that uses them][counters: zero at rest].  The records sit at a
       // FIXED place in front: behind the counters their offset would change with the grid and the batch, and the stale records
       // of one call would be the next layout's counters.
       if (int rc = vox_state_for_stream(stream, kOwnRecordWords + L.s_total * kXcd, &own)) return rc;
-      part = reinterpret_cast<unsigned long long*>(own->words);
-      part2 = own->words + (size_t)L.nchunks * batch * 2;
-      err = own->words + record_words - 4;
-      count = own->words + kOwnRecordWords;
+      records = own.st->words;
+      count = own.st->words + kOwnRecordWords;
     }
   }
-  if (!own) {
-    // (a kernel, not hipMemsetAsync: captured into a HIP graph the memset NODE of this call did not take effect on the second
-    // replay -- counters left dirty, wild offsets, "write access to a read-only page"; scripts/ubench/vox_graph_probe.py)
-    hipLaunchKernelGGL(vox_clear_kernel, dim3((unsigned)std::min<size_t>(ceil_div((int64_t)cleared_words, 1024), 1024)), blk, 0, stream,
-                       reinterpret_cast<unsigned*>(count), (size_t)cleared_words);
-  }
+  unsigned long long* part = reinterpret_cast<unsigned long long*>(records);
+  unsigned* part2 = records + (size_t)L.nchunks * batch * 2;
+  unsigned* err = records + record_words - 4;
+  if (!own.st) vox_fill(count, B.cleared_words, 0u, stream);
   const int tiles = (int)std::max<int64_t>(1, ceil_div(a.max_scene, kTile));
   const bool stage = f <= 8;
   const size_t stage_bytes = stage ? sizeof(float) * ((size_t)kTile * f + 8) : 16;
-  if (stage)
-    hipLaunchKernelGGL(vox_bin_count_kernel<true>, dim3(tiles, batch), blk, stage_bytes, stream, a.points, so, sw, f, a.g, L.bg, count,
-                       pos, flags, own ? reinterpret_cast<unsigned*>(part) : nullptr, (int)(cleared_words - L.s_total * kXcd), g_dbg);
-  else
-    hipLaunchKernelGGL(vox_bin_count_kernel<false>, dim3(tiles, batch), blk, stage_bytes, stream, a.points, so, sw, f, a.g, L.bg, count,
-                       pos, flags, own ? reinterpret_cast<unsigned*>(part) : nullptr, (int)(cleared_words - L.s_total * kXcd), g_dbg);
+  launch_staged(stage, vox_bin_count_kernel<true>, vox_bin_count_kernel<false>, dim3(tiles, batch), stage_bytes, stream,
+                a.points, so, sw, f, a.g, L.bg, count, B.pos, B.flags, own.st ? records : nullptr, (int)record_words, g_dbg);
   EFG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(vox_bin_scan_kernel, dim3(L.nchunks, batch), blk, 0, stream, so, L.bg, count, part, L.nchunks, basex,
-                     small_list, big_list, nlist, err, own ? 1 : 0, g_dbg);
+  hipLaunchKernelGGL(vox_bin_scan_kernel, dim3(L.nchunks, batch), blk, 0, stream, so, L.bg, count, part, L.nchunks, B.basex,
+                     B.small_list, B.big_list, B.nlist, err, own.st ? 1 : 0, g_dbg);
   EFG_LAUNCH_CHECK();
   if (a.n_total > 0) {
-    if (stage)
-      hipLaunchKernelGGL(vox_bin_scatter_kernel<true>, dim3(tiles, batch), blk, stage_bytes, stream, a.points, so, f, a.g, L.bg, pos,
-                         basex, meta, rows, L.rs, g_dbg);
-    else
-      hipLaunchKernelGGL(vox_bin_scatter_kernel<false>, dim3(tiles, batch), blk, stage_bytes, stream, a.points, so, f, a.g, L.bg, pos,
-                         basex, meta, rows, L.rs, g_dbg);
+    launch_staged(stage, vox_bin_scatter_kernel<true>, vox_bin_scatter_kernel<false>, dim3(tiles, batch), stage_bytes,
+                  stream, a.points, so, f, a.g, L.bg, B.pos, B.basex, B.meta, B.rows, L.rs, g_dbg);
     EFG_LAUNCH_CHECK();
   }
   // the bins are listed on the device; a fixed grid loops over them (bounded by what the host knows: a bin holds a point)
@@ -1204,18 +1197,18 @@ int bins_hard_voxelize(const HardArgs& a) {
   // (K4 is light -- 16 KB of LDS, 8 workgroups per CU: every bin gets its own workgroup up to 2048 of them)
   const int gx4 = (int)std::max<int64_t>(1, std::min<int64_t>(items_ub, std::max(256, 2 * kItemGrid / batch)));
   if (a.n_total > 0) {
-    hipLaunchKernelGGL(vox_first_kernel, dim3(gx4, batch), blk, 0, stream, so, sw, L.bg, small_list, big_list, nlist, meta,
-                       flags, g_dbg);
+    hipLaunchKernelGGL(vox_first_kernel, dim3(gx4, batch), blk, 0, stream, so, sw, L.bg, B.small_list, B.big_list, B.nlist,
+                       B.meta, B.flags, g_dbg);
     EFG_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(vox_rank_kernel, dim3(nchunks2, batch), blk, 0, stream, so, sw, flags, part2, nchunks2, bits, prefix,
-                     a.voxel_num, i_break, a.max_voxels, err, g_dbg);
+  hipLaunchKernelGGL(vox_rank_kernel, dim3(nchunks2, batch), blk, 0, stream, so, sw, B.flags, part2, nchunks2, B.bits,
+                     B.prefix, a.voxel_num, i_break, a.max_voxels, err, g_dbg);
   EFG_LAUNCH_CHECK();
   if (a.n_total > 0) {
-#define EFG_VOX_WRITE(KM, FF)                                                                                            \
-  hipLaunchKernelGGL((vox_write_kernel<KM, FF>), dim3(gx, batch), blk, 0, stream, so, sw, L.bg, f, L.rs, small_list,       \
-                     big_list, nlist, meta, rows, bits, prefix, i_break, a.voxel_num, a.max_points, a.coors_cols, a.voxels, \
-                     a.coors, a.npv, a.mean, seg_idx, seg_e, (size_t)L.n, g_dbg)
+#define EFG_VOX_WRITE(KM, FF)                                                                                             \
+  hipLaunchKernelGGL((vox_write_kernel<KM, FF>), dim3(gx, batch), blk, 0, stream, so, sw, L.bg, f, L.rs, B.small_list,     \
+                     B.big_list, B.nlist, B.meta, B.rows, B.bits, B.prefix, i_break, a.voxel_num, a.max_points,             \
+                     a.coors_cols, a.voxels, a.coors, a.npv, a.mean, B.seg_idx, B.seg_e, (size_t)L.n, g_dbg)
     if (a.max_points == 5 && f == 5) EFG_VOX_WRITE(5, 5);
     else if (a.max_points == 5 && f == 6) EFG_VOX_WRITE(5, 6);
     else if (a.max_points <= 5 && f <= 8) EFG_VOX_WRITE(5, 0);
@@ -1224,7 +1217,7 @@ int bins_hard_voxelize(const HardArgs& a) {
 #undef EFG_VOX_WRITE
     EFG_LAUNCH_CHECK();
   }
-  if (own) vox_state_done(own);
+  own.clean = true;
   return EFG_OK;
 }
 

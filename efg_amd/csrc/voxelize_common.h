@@ -42,6 +42,22 @@ __device__ __forceinline__ bool point_cell(const float* __restrict__ p, const Vo
   return cell_of(p[0], p[1], p[2], g, cx, cy, cz);
 }
 
+// p[0 .. n) = v: the words of a call that a kernel has to initialise (a kernel, not hipMemsetAsync: captured into a
+// HIP graph the memset NODE of a call did not take effect on the second replay -- scripts/ubench/vox_graph_probe.py)
+namespace {
+__global__ void __launch_bounds__(256) vox_fill_kernel(unsigned* __restrict__ p, size_t n, unsigned v) {
+  for (size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x; i < n; i += (size_t)gridDim.x * 1024) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (i + u * 256 < n) p[i + u * 256] = v;
+  }
+}
+inline void vox_fill(unsigned* p, size_t n, unsigned v, hipStream_t stream) {
+  hipLaunchKernelGGL(vox_fill_kernel, dim3((unsigned)std::min<size_t>(ceil_div((int64_t)n, 1024), 1024)), dim3(256), 0,
+                     stream, p, n, v);
+}
+}  // namespace
+
 // arguments of efg_hard_voxelize_f32 after validation (host side)
 struct HardArgs {
   const float* points;

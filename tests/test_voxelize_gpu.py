@@ -1,5 +1,6 @@
 """GPU parity: HIP voxelizers (through the C ABI) vs the oracle and the reference's golden
 vectors.  Bar: bit-exact (integer indices, copied fp32 payloads)."""
+import functools
 import glob
 import os
 
@@ -230,6 +231,127 @@ def test_library_state_survives_changing_layouts(dev, oracle_mod, monkeypatch):
             assert np.array_equal(out["coordinates"][base:base + m].cpu().numpy()[:, 1:], ec)
             base += m
         _check_vs_oracle(dev, oracle_mod, waymo[0], VOXEL_SIZE, PC_RANGE, 5, 120000)
+
+
+_SMALL_VS, _SMALL_CR = [0.1, 0.1, 0.1], [0.0, 0.0, 0.0, 3.2, 3.2, 3.2]   # grid 32 x 32 x 32: 4 x 4 x 1 supercells
+_SMALL_MV = (20000, 3000)            # max_voxels that does not bind / whose `break` falls inside the crowded column
+_SMALL_ORACLE = {}                   # (scene, max_points, f, max_voxels) -> oracle result, shared by both implementations
+
+
+@functools.lru_cache(maxsize=None)
+def _bin_class_scenes():
+    """20 000 points x 9 features over 16 supercells: a uniform part, one column crowded enough for a four-way split of
+    the write kernel, one for a two-way split, one bin for a single workgroup, 3 % of the points outside the range.
+    Second scene: the same points in reverse order."""
+    rng = np.random.default_rng(31)
+
+    def column(x0, n):   # one supercell column: 8 x 8 cells from (x0, 0), all 32 cells high
+        return np.stack([rng.uniform(x0, x0 + 0.8, n), rng.uniform(0.0, 0.8, n), rng.uniform(0.0, 3.2, n)], 1)
+
+    outside = rng.uniform(0.0, 3.2, (600, 3))
+    outside[:300, 0] = rng.uniform(3.2, 3.6, 300)
+    outside[300:, 2] = rng.uniform(-0.4, -0.01, 300)
+    xyz = np.concatenate([rng.uniform(0.0, 3.2, (3000, 3)), column(0.0, 15000), column(0.8, 1000), column(1.6, 400),
+                          outside])
+    pts = np.concatenate([xyz, rng.uniform(-1.0, 1.0, (len(xyz), 6))], 1).astype(np.float32)
+    rng.shuffle(pts)
+    return pts, np.ascontiguousarray(pts[::-1])
+
+
+def _small_oracle(oracle_mod, scene, mp, f, mv):
+    key = (scene, mp, f, mv)
+    if key not in _SMALL_ORACLE:
+        pts = np.ascontiguousarray(_bin_class_scenes()[scene][:, :f])
+        _SMALL_ORACLE[key] = oracle_mod.hard_voxelize(pts, _SMALL_VS, _SMALL_CR, mp, mv)
+    return _SMALL_ORACLE[key]
+
+
+@functools.lru_cache(maxsize=None)
+def _assert_bin_classes():
+    """The condition on the input, in numpy: supercell = 8 x 8 x min(grid_z, 40) cells; the write kernel takes bins of
+    <= 256 points by one wave, <= 768 by one workgroup, <= 1536 by two (cells by x parity), more by four (x and y
+    parity); a workgroup's share above 1024 points is sorted through global scratch instead of LDS."""
+    pts = _bin_class_scenes()[0]
+    cell = np.floor(pts[:, :3] / np.float32(0.1))          # fp32 division, like the kernels (range minimum 0)
+    inside = ((cell >= 0) & (cell < 32)).all(1)
+    assert 0.02 < 1.0 - inside.mean() < 0.05
+    cx, cy, cz = cell[inside].astype(np.int64).T
+    sc = (cy >> 3) * 4 + (cx >> 3)
+    counts = np.bincount(sc, minlength=16)
+    assert ((counts > 0) & (counts <= 256)).any()
+    assert ((counts > 256) & (counts <= 768)).any()
+    assert ((counts > 768) & (counts <= 1536)).any()
+    assert (counts > 1536).any()
+    crowded = int(counts.argmax())
+    part = (cx & 1) | ((cy & 1) << 1)
+    assert np.bincount(part[sc == crowded], minlength=4).max() > 1024
+    # the smaller max_voxels binds, and its `break` leaves part of the crowded column on either side -- still more than
+    # 1024 points of one part before it
+    flat = (cz * 32 + cy) * 32 + cx
+    first = np.sort(np.unique(flat, return_index=True)[1])
+    assert _SMALL_MV[1] < len(first) <= _SMALL_MV[0]
+    before = np.arange(len(flat)) < first[_SMALL_MV[1]]
+    in_crowded = sc == crowded
+    assert (in_crowded & before).any() and (in_crowded & ~before).any()
+    assert np.bincount(part[in_crowded & before], minlength=4).max() > 1024
+
+
+def test_small_cloud_bin_classes_and_eight_slot_write(dev, oracle_mod, impl):
+    """Every bin-size class of the binned voxelizer, the 8-slot write kernel (5 < max_points <= 8, which no other case
+    runs) and the other run-time-sized ones, at 20 000 points: single scenes with three coordinate columns, then two
+    scenes in one call with four columns and the fused mean."""
+    from efg_amd.operators import voxelize_batch
+
+    _assert_bin_classes()
+    scenes = _bin_class_scenes()
+    for mp, f in [(6, 4), (7, 7), (8, 8), (5, 7), (9, 8), (5, 9)]:
+        for mv in _SMALL_MV:
+            ev, ec, en = _small_oracle(oracle_mod, 0, mp, f, mv)
+            assert (ev.shape[0] == mv) == (mv == _SMALL_MV[1])
+            v, c, k = _run_hard(dev, np.ascontiguousarray(scenes[0][:, :f]), _SMALL_VS, _SMALL_CR, mp, mv)
+            assert v.shape == ev.shape
+            assert np.array_equal(c, ec) and np.array_equal(k, en) and np.array_equal(v, ev)
+            out = voxelize_batch([torch.from_numpy(np.ascontiguousarray(s[:, :f])).to(dev) for s in scenes], _SMALL_VS,
+                                 _SMALL_CR, mp, mv)
+            base = 0
+            for b in range(2):
+                ev, ec, en = _small_oracle(oracle_mod, b, mp, f, mv)
+                m = out["num_voxels"][b]
+                assert m == ev.shape[0]
+                sl = slice(base, base + m)
+                assert np.array_equal(out["voxels"][sl].cpu().numpy(), ev)
+                co = out["coordinates"][sl].cpu().numpy()
+                assert (co[:, 0] == b).all() and np.array_equal(co[:, 1:], ec)
+                assert np.array_equal(out["num_points_per_voxel"][sl].cpu().numpy(), en)
+                acc = np.zeros((m, f), np.float32)
+                for slot in range(mp):                      # fp32 sum in slot order (empty slots hold zeros), one division
+                    acc = acc + ev[:, slot, :]
+                assert acc.dtype == np.float32
+                assert np.array_equal(out["voxel_mean"][sl].cpu().numpy(), acc / en[:, None].astype(np.float32))
+                base += m
+            assert out["voxels"].shape[0] == base
+
+
+def test_more_streams_than_the_state_pool_keeps(dev, oracle_mod, monkeypatch):
+    """The binned path keeps its self-cleaning counters per (device, stream) and recycles idle entries beyond 32: the same
+    cloud on the default stream, on 34 further streams one after the other, then on the first of them again."""
+    from efg_amd.operators import voxelization
+
+    monkeypatch.setenv("EFG_VOX_IMPL", "bins")
+    mp, f, mv = 5, 5, _SMALL_MV[0]
+    want = _small_oracle(oracle_mod, 0, mp, f, mv)
+    t = torch.from_numpy(np.ascontiguousarray(_bin_class_scenes()[0][:, :f])).to(dev)
+    # (two priorities: streams of one priority come from a pool that hands the same 32 out again)
+    streams = [torch.cuda.Stream(device=dev, priority=-(i & 1)) for i in range(34)]
+    assert len({s.cuda_stream for s in streams}) == 34
+    main = torch.cuda.current_stream(dev)
+    for s in [main] + streams + streams[:1]:
+        s.wait_stream(main)
+        with torch.cuda.stream(s):
+            got = [o.cpu().numpy() for o in voxelization(t, _SMALL_VS, _SMALL_CR, mp, mv)]
+        main.wait_stream(s)
+        assert got[0].shape == want[0].shape
+        assert all(np.array_equal(g, w) for g, w in zip(got, want))
 
 
 def test_full_size_both_implementations_agree(dev, impl, oracle_mod):
