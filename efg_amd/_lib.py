@@ -136,6 +136,9 @@ _SIGS = {
     "efg_det_eval_pair_weights_f32": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_float] * 3 + [c_void_p, c_void_p]),
     "efg_det_eval_assign_f32": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p] * 7),
     "efg_det_eval_accumulate": (c_int, [c_void_p, c_void_p, c_void_p, c_int] + [c_void_p] * 3),
+    "efg_track_eval_mot_f32": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 5 + [c_int, c_void_p, c_int] +
+                               [c_void_p] * 3),
+    "efg_track_eval_accumulate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 3),
 }
 
 # the split-precision GEMM arms (csrc/gemm_split_bf16.h): one set of six signatures under two prefixes

@@ -13,16 +13,8 @@
 //     one at a time by a shortest augmenting path (the Hungarian / Jonker-Volgenant row insertion that matcher.hip and
 //     scipy run, here on costs -w), after which the assignment is optimal for the rows inserted so far; whenever the
 //     prefix length passes a cutoff boundary the counts of that cutoff are written.
-//       - every row has a zero-weight column of its own ("unmatched").  It is adjacent to that row only, so it never
-//         enters the search tree once assigned, its dual stays 0, and all the kernel keeps of those columns is the best
-//         one seen in the current search (s_dval / s_drow): a row of the tree at path cost d may leave to its own column
-//         at cost d - u[row].
-//       - pairs of weight 0 are no edges.  A search ends at a free ground truth or at an own column; each step before
-//         that visits a new ground-truth column, so an insertion takes at most n_gt + 1 steps: the step loop is a
-//         counted loop, and a value that is not a finite positive weight is no edge, so no input steers it.
-//       - duals are fp64 sums and differences of fp32 weights in [0.5, 1]: exact.
-//     Column state and duals live in LDS (32 B per column, 16 B per row), weights are read from global memory (a row is
-//     one coalesced read), the column scan is one column per thread with a block-wide argmin: two barriers per step.
+//     The insertion itself (own zero-weight columns, weight-0 pairs as non-edges, the counted step loop, fp64 duals in
+//     LDS, one column per thread with a block-wide argmin) is row_insert.h, shared with track_eval.hip.
 //
 //   * accumulate_kernel: adds the per-problem tables to the running totals in problem order (one thread per (class,
 //     cutoff) slot walks the problems): integers as int64, heading accuracy in fp64.  Heading accuracy of a pair is
@@ -30,20 +22,17 @@
 //     how frames were grouped into calls or ranks.
 #include "common.h"
 #include "iou3d_pair.h"
+#include "row_insert.h"
 
 #include <math.h>
 
 namespace efg {
 namespace {
 
-constexpr int kEvalThreads = 256;
-constexpr int kMaxPred = 1024;  // rows (predictions of one class in one frame)
-constexpr int kMaxGt = 256;     // columns (ground truths of one class in one frame) == kEvalThreads: one column per thread
 constexpr int kCutoffs = 101;
 constexpr int kNumCounts = 5;   // tp1, tp2, fp, fn1, fn2
 constexpr int kNumSums = 3;     // ha1, ha2, matched weight
 constexpr int kProbFields = 6;  // frame, first prediction, predictions, first ground truth, ground truths, class
-static_assert(kMaxGt == kEvalThreads, "one column per thread");
 
 __global__ __launch_bounds__(kPairThreads) void pair_weight_kernel(
     const float* __restrict__ pred_boxes, const int* __restrict__ pred_labels, const int* __restrict__ pred_off,
@@ -105,26 +94,6 @@ __global__ __launch_bounds__(kPairThreads) void pair_weight_kernel(
   if (q.n > 0) drain();
 }
 
-struct Cand {
-  double val;
-  int key;  // (assigned ? 1 << 30 : 0) + column: smaller wins, so a free column ends the search before a longer path
-};
-
-__device__ __forceinline__ bool better(const Cand& a, const Cand& b) {
-  return a.val < b.val || (a.val == b.val && a.key < b.key);
-}
-
-__device__ __forceinline__ Cand wave_min(Cand c) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    Cand o;
-    o.val = __shfl_xor(c.val, d, 64);
-    o.key = __shfl_xor(c.key, d, 64);
-    if (better(o, c)) c = o;
-  }
-  return c;
-}
-
 __device__ __forceinline__ double wave_sum(double v) {  // xor butterfly: every lane ends with the same bits
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
@@ -153,17 +122,9 @@ __global__ __launch_bounds__(kEvalThreads) void prefix_assign_kernel(
     const int* __restrict__ gt_off, const int* __restrict__ prob, const float* __restrict__ scores,
     const float* __restrict__ pred_boxes, const float* __restrict__ gt_boxes, const int* __restrict__ gt_level,
     int* __restrict__ counts, double* __restrict__ sums) {
-  __shared__ double s_u[kMaxPred];   // row duals
-  __shared__ double s_spc[kMaxGt];   // shortest path cost of the current search
-  __shared__ double s_v[kMaxGt];     // column duals
-  __shared__ int s_col4row[kMaxPred];
-  __shared__ int s_sr[kMaxGt + 1];   // rows of the current search tree
-  __shared__ int s_path[kMaxGt], s_row4col[kMaxGt], s_vis[kMaxGt];
-  __shared__ Cand wave_best[kEvalThreads / 64];
+  __shared__ RowInsertLds lds;  // row_insert.h
   __shared__ double red_d[kEvalThreads / 64][kNumSums];
   __shared__ int red_i[kEvalThreads / 64][kNumCounts];
-  __shared__ int s_i, s_sink, s_done, s_nsr, s_drow;
-  __shared__ double s_min_val, s_dval;
 
   const int p = blockIdx.x, tid = threadIdx.x;
   const int* d = prob + (int64_t)p * kProbFields;
@@ -175,8 +136,8 @@ __global__ __launch_bounds__(kEvalThreads) void prefix_assign_kernel(
   double* out_d = sums + (int64_t)p * kCutoffs * kNumSums;
 
   if (tid < ng) {
-    s_v[tid] = 0.0;
-    s_row4col[tid] = -1;
+    lds.v[tid] = 0.0;
+    lds.row4col[tid] = -1;
   }
   __syncthreads();
 
@@ -186,7 +147,7 @@ __global__ __launch_bounds__(kEvalThreads) void prefix_assign_kernel(
     double s[kNumSums] = {0.0, 0.0, 0.0};
     int matched = 0;
     if (tid < ng) {
-      const int r = s_row4col[tid], lv = gt_level[g0 + tid];
+      const int r = lds.row4col[tid], lv = gt_level[g0 + tid];
       if (r >= 0) {
         matched = 1;
         const double acc = heading_accuracy(pred_boxes[(int64_t)(r0 + r) * 7 + 6], gt_boxes[(int64_t)(g0 + tid) * 7 + 6]);
@@ -230,96 +191,7 @@ __global__ __launch_bounds__(kEvalThreads) void prefix_assign_kernel(
   for (int cur = 0; cur < np; ++cur) {
     const int hi = last_cutoff(scores[r0 + cur]);
     if (hi < 0) break;  // sorted by descending score: this row and the ones behind it are never in play
-    if (tid < ng) {
-      s_spc[tid] = INFINITY;
-      s_vis[tid] = 0;
-    }
-    if (tid == 0) {
-      s_i = cur;
-      s_sink = -1;
-      s_done = 0;
-      s_nsr = 0;
-      s_min_val = 0.0;
-      s_dval = INFINITY;
-      s_drow = cur;
-      s_u[cur] = 0.0;
-      s_col4row[cur] = -1;
-    }
-    __syncthreads();
-
-    // every step that does not end the search visits a new column: at most ng + 1 steps
-    for (int step = 0; step <= ng; ++step) {
-      const int i = s_i;
-      const double min_val = s_min_val, ui = s_u[i];
-      Cand best{INFINITY, 0x7fffffff};
-      if (tid < ng && !s_vis[tid]) {
-        const float wt = w[(int64_t)i * gf + tid];
-        double s = s_spc[tid];
-        if (wt > 0.0f && wt < INFINITY) {  // anything else is no edge
-          const double r = min_val - (double)wt - ui - s_v[tid];
-          if (r < s) {
-            s_path[tid] = i;
-            s_spc[tid] = s = r;
-          }
-        }
-        if (s < INFINITY) best = Cand{s, (s_row4col[tid] >= 0 ? (1 << 30) : 0) + tid};
-      }
-      best = wave_min(best);
-      if ((tid & 63) == 0) wave_best[tid >> 6] = best;
-      __syncthreads();
-      if (tid == 0) {
-        Cand b = wave_best[0];
-#pragma unroll
-        for (int wv = 1; wv < kEvalThreads / 64; ++wv)
-          if (better(wave_best[wv], b)) b = wave_best[wv];
-        s_sr[s_nsr++] = i;
-        const double dv = min_val - ui;  // row i may leave to its own zero-weight column
-        if (dv < s_dval) {
-          s_dval = dv;
-          s_drow = i;
-        }
-        if (b.val < s_dval) {  // false for NaN: the search then ends at an own column
-          const int j = b.key & ((1 << 30) - 1);
-          s_min_val = b.val;
-          s_vis[j] = 1;
-          if (s_row4col[j] < 0) {
-            s_sink = j;
-            s_done = 1;
-          } else {
-            s_i = s_row4col[j];
-          }
-        } else {
-          s_min_val = s_dval;
-          s_sink = -1;
-          s_done = 1;
-        }
-      }
-      __syncthreads();
-      if (s_done) break;
-    }
-
-    if (s_done) {  // always, by the step count above
-      const double min_val = s_min_val;
-      const int nsr = s_nsr;
-      for (int t = tid; t < nsr; t += kEvalThreads) {
-        const int r = s_sr[t], cj = s_col4row[r];  // every tree row but `cur` was reached through its column
-        s_u[r] += (r == cur || cj < 0) ? min_val : min_val - s_spc[cj];
-      }
-      __syncthreads();  // u reads col4row / spc before they change below
-      if (tid < ng && s_vis[tid]) s_v[tid] -= min_val - s_spc[tid];
-      if (tid == 0) {  // augment along the path, from the sink back to the inserted row
-        int j = s_sink, r = j >= 0 ? s_path[j] : s_drow;
-        for (int t = 0; t <= ng; ++t) {
-          const int old = s_col4row[r];
-          s_col4row[r] = j;
-          if (j >= 0) s_row4col[j] = r;
-          if (r == cur || old < 0) break;
-          j = old;
-          r = s_path[j];
-        }
-      }
-    }
-    __syncthreads();
+    insert_row(lds, w, gf, ng, tid < ng, cur, tid);
 
     const int lo = cur + 1 < np ? last_cutoff(scores[r0 + cur + 1]) : -1;
     if (hi > lo) emit(cur + 1, lo + 1, hi);

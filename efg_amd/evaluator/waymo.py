@@ -104,7 +104,7 @@ class WaymoDetEvaluator(DatasetEvaluator):
         ps, pl = _np(output["scores"], np.float32).reshape(-1), _np(output["labels"], np.int64).reshape(-1)
         keep = self._in_range(pb) & (pl >= 1) & (pl <= 3)
         keep[keep] = self._class_on[pl[keep]]
-        pb, ps, pl = pb[keep], ps[keep], pl[keep]
+        pb, ps, pl, pi = pb[keep], ps[keep], pl[keep], np.nonzero(keep)[0]
 
         gb = _np(target["gt_boxes"], np.float32)
         gb = gb.reshape(-1, gb.shape[-1] if gb.ndim == 2 else 7)[:, [0, 1, 2, 3, 4, 5, -1]]
@@ -115,9 +115,10 @@ class WaymoDetEvaluator(DatasetEvaluator):
         level = np.where(diff == 0, np.where(npts > 5, 1, 2), diff)
         keep = self._in_range(gb) & (npts > 0) & (gl >= 1) & (gl <= 3)
         keep[keep] = self._class_on[gl[keep]]
-        gb, gl, level = gb[keep], gl[keep], level[keep]
+        gb, gl, level, gi = gb[keep], gl[keep], level[keep], np.nonzero(keep)[0]
         pb[:, 6], gb[:, 6] = _wrap(pb[:, 6]), _wrap(gb[:, 6])
-        return {"pb": pb, "ps": ps, "pl": pl, "gb": gb, "gl": gl, "level": level.astype(np.int32)}
+        # pi / gi: the rows of the output / target that the other arrays hold, through every mask and permutation
+        return {"pb": pb, "ps": ps, "pl": pl, "pi": pi, "gb": gb, "gl": gl, "level": level.astype(np.int32), "gi": gi}
 
     def _prepare(self, inputs, outputs):
         frames = [self._frame(self._target(i), o) for i, o in zip(inputs, outputs)]
@@ -129,9 +130,9 @@ class WaymoDetEvaluator(DatasetEvaluator):
             # class-major, descending score inside a class, the lower index first among equal scores
             ps = np.where(np.isnan(f["ps"]), -np.inf, f["ps"]).astype(np.float32)
             order = np.lexsort((np.arange(len(ps)), -ps, f["pl"]))
-            f["pb"], f["ps"], f["pl"] = f["pb"][order], ps[order], f["pl"][order]
+            f["pb"], f["ps"], f["pl"], f["pi"] = f["pb"][order], ps[order], f["pl"][order], f["pi"][order]
             order = np.argsort(f["gl"], kind="stable")
-            f["gb"], f["gl"], f["level"] = f["gb"][order], f["gl"][order], f["level"][order]
+            f["gb"], f["gl"], f["level"], f["gi"] = f["gb"][order], f["gl"][order], f["level"][order], f["gi"][order]
         return frames
 
     def _device_of(self, outputs):

@@ -71,7 +71,9 @@ def make_tracking_sequence(seed, frames=8, n_objects=10, n_ground=4000, per_obje
     """A short drive for the online tracker ($TF/trajectoryformer.py:forward_inference): objects with constant global
     velocity, an ego pose that advances and yaws a little every 0.1 s, and per frame the detector's boxes in the
     vehicle frame (jitter, misses, a few low-score ghosts), a small current-sweep cloud (ground + object surfaces,
-    columns x y z intensity elongation dt) and the reference's frame token.  Returns a list of `(sample, info)`."""
+    columns x y z intensity elongation dt) and the reference's frame token.  The annotations also hold the objects
+    themselves for the tracking evaluator (gt_boxes in the vehicle frame, labels, gt_ids, difficulty, num_points_in_gt),
+    built from the states above without a generator draw.  Returns a list of `(sample, info)`."""
     rng = np.random.default_rng(seed)
     labels = rng.choice([1, 1, 1, 2, 3], n_objects).astype(np.float32)
     size = np.array([{1: (4.6, 2.0, 1.7), 2: (0.9, 0.8, 1.8), 3: (1.8, 0.7, 1.7)}[int(c)] for c in labels])
@@ -115,7 +117,12 @@ def make_tracking_sequence(seed, frames=8, n_objects=10, n_ground=4000, per_obje
         pts = np.concatenate([xyz, np.tanh(rng.uniform(0, 2, (len(xyz), 1))), rng.uniform(0, 1.5, (len(xyz), 1)),
                               np.zeros((len(xyz), 1))], 1).astype(np.float32)
         pts = pts[rng.permutation(len(pts))]
+        gt_boxes = np.concatenate([centre, pos0[:, 2:3], size, (yaw - ego_yaw)[:, None]], 1).astype(np.float32)
         info = {"token": "segment-%d_frame_%d.npy" % (seed, f), "veh_to_global": pose,
-                "annotations": {"pred_boxes3d": boxes, "pred_scores": scores, "pred_labels": lab}}
+                "annotations": {"pred_boxes3d": boxes, "pred_scores": scores, "pred_labels": lab,
+                                "gt_boxes": gt_boxes, "labels": labels.astype(np.int64),
+                                "gt_ids": np.array(["object-%d" % k for k in range(n_objects)]),
+                                "difficulty": np.zeros(n_objects, np.int64),
+                                "num_points_in_gt": np.full(n_objects, per_object, np.int64)}}
         out.append(([{"points": np.ascontiguousarray(pts)}], info))
     return out

@@ -663,6 +663,35 @@ int efg_det_eval_assign_f32(const float* weights, const int64_t* blk_off, const 
 int efg_det_eval_accumulate(const int32_t* counts, const double* sums, const int32_t* problems, int n_problems,
                             int64_t* total_counts, double* total_sums, void* stream);
 
+/* ---- tracking evaluation: Waymo-protocol CLEAR MOT counts (track_eval.hip, DESIGN.md "Tracking evaluation") ----
+ * Same frame-segmented (CSR) layout as the detection block, tracks standing where predictions do: frame f owns rows
+ * trk_off[f]..trk_off[f+1] and gt_off[f]..gt_off[f+1] (int32 [n_frames + 1]) and the weight block at weights + blk_off[f]
+ * (row stride G_f), written by efg_det_eval_pair_weights_f32.  Inside a frame, tracks are sorted class-major by descending
+ * score (scores fp32 [sum P]), ground truths class-major by ascending gt_ids.
+ *   mot: ranges int32 [n_frames, 3, 4] = (first track, tracks, first ground truth, ground truths) of every (frame, class),
+ *     global indices; problems int32 [n_problems, 3] = (first frame, end frame, class 0..2): one class of one segment, a
+ *     run of consecutive frames of one sequence.  track_ids int32 [sum P] >= 0, unique within a frame; gt_ids int32
+ *     [sum G] in 0..capacity-1, unique within a frame, disjoint between the segments of different sequences; gt_level
+ *     int32 [sum G].  cutoffs fp32 [n_cutoffs] ascending, 1 <= n_cutoffs <= 101; a track is in play at
+ *     cutoff k iff score >= cutoffs[k].  last int32 [n_cutoffs, capacity], input and output: the track that ground truth
+ *     gt_id was most recently matched to at cutoff k, -1 if none.  One workgroup per (problem, cutoff) walks the frames in
+ *     order: a ground truth keeps its last track if that track is in play and the pair's weight is > 0 (two ground truths
+ *     claiming one track: the lower gt_id keeps it), the rest get the maximum-weight assignment, then last is updated.
+ *     counts int32 [n_problems, n_cutoffs, 9] = (matches at level 1, level 2, tracks in play in no pair, unmatched ground
+ *     truths of level <= 1, <= 2, mismatches at level 1, level 2, ground truths of level <= 1, <= 2) and sums fp64
+ *     [n_problems, n_cutoffs, 2] = sum of 1 - weight over the matches of level <= 1, <= 2, each term rounded to a multiple
+ *     of 2^-30.  max_tracks / max_gt: the largest (frame, class) of the call; more than efg_det_eval_max_pred() tracks or
+ *     efg_det_eval_max_gt() ground truths is an error, nothing is truncated.
+ *   accumulate: total_counts int64 [3, n_cutoffs, 9] and total_sums fp64 [3, n_cutoffs, 2] += the problems of each class,
+ *     in problem order (no atomics: the same bits every run). */
+int efg_track_eval_mot_f32(const float* weights, const int64_t* blk_off, const int32_t* trk_off, const int32_t* gt_off,
+                           const int32_t* ranges, const int32_t* problems, int n_problems, int n_frames, int max_tracks,
+                           int max_gt, const float* scores, const int32_t* track_ids, const int32_t* gt_ids,
+                           const int32_t* gt_level, const float* cutoffs, int n_cutoffs, int32_t* last, int capacity,
+                           int32_t* counts, double* sums, void* stream);
+int efg_track_eval_accumulate(const int32_t* counts, const double* sums, const int32_t* problems, int n_problems,
+                              int n_cutoffs, int64_t* total_counts, double* total_sums, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
