@@ -139,6 +139,10 @@ _SIGS = {
     "efg_track_eval_mot_f32": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p] * 5 + [c_int, c_void_p, c_int] +
                                [c_void_p] * 3),
     "efg_track_eval_accumulate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 3),
+    "efg_nusc_eval_max_gt": (c_int, []),
+    "efg_nusc_eval_match_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int64, c_int64] + [c_float] * 4 +
+                                [c_void_p, c_void_p]),
+    "efg_nusc_eval_errors_f32": (c_int, [c_void_p] * 6 + [c_int64, c_int64, c_int] + [c_void_p] * 3),
 }
 
 # the split-precision GEMM arms (csrc/gemm_split_bf16.h): one set of six signatures under two prefixes

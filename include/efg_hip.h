@@ -692,6 +692,30 @@ int efg_track_eval_mot_f32(const float* weights, const int64_t* blk_off, const i
 int efg_track_eval_accumulate(const int32_t* counts, const double* sums, const int32_t* problems, int n_problems,
                               int n_cutoffs, int64_t* total_counts, double* total_sums, void* stream);
 
+/* ---- nuScenes detection evaluation: greedy centre-distance matching (nusc_eval.hip, DESIGN.md "nuScenes detection
+ * evaluation") ----
+ * The (frame, class) CSR layout of the detection block: the predictions and ground truths of the frames of one call are
+ * concatenated; boxes are fp32 [n, 9] = (x, y, z, l, w, h, yaw, vx, vy).  problems int32 [n_problems, 5] = (first
+ * prediction, predictions, first ground truth, ground truths, class), global rows; the predictions of a problem are sorted
+ * by descending score.
+ *   match: one workgroup per problem, one wave per distance threshold thr0..thr3.  In score order a prediction takes the
+ *     nearest ground truth of its problem not yet taken at that threshold (distance sqrt(dx * dx + dy * dy) in fp64 on the
+ *     fp32 centres; equal distances: the lowest row) if that distance is < the threshold.  match int32 [4, n_pred]: the
+ *     global ground-truth row, or -1; the caller fills it with -1 beforehand (rows no problem covers keep that).
+ *     max_gt: the largest problem of the call; more than efg_nusc_eval_max_gt() ground truths in one problem is an
+ *     error, nothing is truncated.
+ *   errors: tp_bits int32 [n_pred] = bit t set where match[t] >= 0; err fp64 [n_pred, 5] = (translation, scale,
+ *     orientation, velocity, attribute) error against the ground truth match[2], NaN where there is none, where the
+ *     ground truth's velocity is NaN (velocity) or its attribute code gt_attr is < 0 (attribute).  pred_class int32
+ *     [n_pred]; the orientation error has period pi for pred_class == barrier_class and 2 pi otherwise. */
+int efg_nusc_eval_max_gt(void);
+int efg_nusc_eval_match_f32(const float* pred_boxes, const float* gt_boxes, const int32_t* problems, int n_problems,
+                            int max_gt, int64_t n_pred, int64_t n_gt, float thr0, float thr1, float thr2, float thr3,
+                            int32_t* match, void* stream);
+int efg_nusc_eval_errors_f32(const float* pred_boxes, const int32_t* pred_attr, const int32_t* pred_class,
+                             const float* gt_boxes, const int32_t* gt_attr, const int32_t* match, int64_t n_pred,
+                             int64_t n_gt, int barrier_class, int32_t* tp_bits, double* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
