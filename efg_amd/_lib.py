@@ -143,6 +143,11 @@ _SIGS = {
     "efg_nusc_eval_match_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int64, c_int64] + [c_float] * 4 +
                                 [c_void_p, c_void_p]),
     "efg_nusc_eval_errors_f32": (c_int, [c_void_p] * 6 + [c_int64, c_int64, c_int] + [c_void_p] * 3),
+    "efg_center_decode_max_cells": (c_int, []),
+    "efg_center_decode_max_tasks": (c_int, []),
+    "efg_center_decode_candidates_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_float] * 6 + [c_void_p] * 6),
+    "efg_circle_nms_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p, c_int, c_int] + [c_void_p] * 3),
+    "efg_center_decode_boxes_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 10),
 }
 
 # the split-precision GEMM arms (csrc/gemm_split_bf16.h): one set of six signatures under two prefixes

@@ -244,10 +244,20 @@ class CenterHead(nn.Module):
     # ---- inference --------------------------------------------------------------------------------------------
     @torch.no_grad()
     def predict(self, example, preds_dicts, test_config):
-        """Decode every BEV cell into a box, threshold, rotated NMS on the GPU (csrc/iou3d_nms.hip); the plain path of
-        $CP1/center_head.py:173-386 (no double-flip test-time augmentation, no circular NMS)."""
-        if test_config.get("double_flip", False) or test_config.get("circular_nms", False):
-            raise NotImplementedError("double_flip / circular_nms inference is not mirrored")
+        """-> per scene {"scores", "labels" (1-based, offset by task), "boxes3d"} on the CPU, tasks concatenated in order.
+
+        Default: decode every BEV cell into a box, threshold, rotated NMS on the GPU (csrc/iou3d_nms.hip); the plain path
+        of $CP1/center_head.py:173-386.
+        `circular_nms: True` (the nuScenes experiment's $CP1-nuScenes/center_head.py:316-321 + circle_nms_jit.py): greedy
+        by descending score (equal scores: ascending cell index), a kept centre suppresses every later one whose SQUARED
+        distance is <= `min_radius[task]`, the first `nms.nms_post_max_size` kept per (task, scene).  GPU maps take the
+        device chain (csrc/center_decode.hip: three launches and one copy to the host per call, only the kept cells are
+        decoded), CPU maps the host formulation (circular_host.py).  DESIGN.md "CenterPoint circular-NMS inference".
+        No double-flip test-time augmentation."""
+        if test_config.get("double_flip", False):
+            raise NotImplementedError("double_flip inference is not mirrored")
+        if test_config.get("circular_nms", False):
+            return self._predict_circular(preds_dicts, test_config)
         dev = preds_dicts[0]["hm"].device
         limit = test_config.post_center_limit_range
         limit = torch.tensor(limit, dtype=torch.float32, device=dev) if len(limit) > 0 else None
@@ -283,6 +293,15 @@ class CenterHead(nn.Module):
             results.append({"scores": torch.cat(scores).cpu(), "labels": (torch.cat(labels) + 1).cpu(),
                             "boxes3d": torch.cat(boxes).cpu()})
         return results
+
+    def _predict_circular(self, preds_dicts, test_config):
+        from .circular_host import predict_circular_host
+
+        if preds_dicts[0]["hm"].is_cuda:
+            from ..operators.center_decode import predict_circular_device
+
+            return predict_circular_device(preds_dicts, test_config, self.num_classes)
+        return predict_circular_host(preds_dicts, test_config, self.num_classes)
 
     @staticmethod
     def _post_process(batch_boxes, batch_hm, cfg, limit):

@@ -716,6 +716,41 @@ int efg_nusc_eval_errors_f32(const float* pred_boxes, const int32_t* pred_attr, 
                              const float* gt_boxes, const int32_t* gt_attr, const int32_t* match, int64_t n_pred,
                              int64_t n_gt, int barrier_class, int32_t* tp_bits, double* err, void* stream);
 
+/* ---- CenterPoint inference with the circular NMS (center_decode.hip, DESIGN.md "CenterPoint circular-NMS inference")
+ * ----
+ * The head's maps are NHWC-contiguous fp32 on the device, the same [batch, h, w] for every task.  maps: HOST array
+ * [n_tasks * 6] of device pointers, per task (hm [.., classes], reg [.., 2], height [.., 1], dim [.., 3], rot [.., 2],
+ * vel [.., 2] or NULL -- for all tasks or for none); num_classes: HOST int32 [n_tasks].  At most
+ * efg_center_decode_max_tasks() tasks and efg_center_decode_max_cells() cells (h * w) per map; more is an error, nothing
+ * is truncated.  A segment is one (scene, task), numbered scene * n_tasks + task.
+ *   candidates: per cell score = max_c sigmoid(hm[c]) (label: the lowest c at the maximum), x = ((ix + reg0) *
+ *     out_size_factor) * voxel_x + range_x, y alike from iy, reg1, voxel_y, range_y, z = height.  A cell is a candidate
+ *     iff score > score_threshold and (x, y, z) lies inside limit (HOST float [6] = low xyz, high xyz, both sides
+ *     inclusive; NULL: no range test).  score / label / x / y [batch * n_tasks, h * w]; the score of a cell that is no
+ *     candidate is -inf.
+ *   circle_nms: n_segments lists of segment_len (x, y, score) each, one workgroup per segment; entries whose score is
+ *     -inf (or NaN) take no part.  Greedy by descending score, equal scores by ascending index: an entry not yet
+ *     suppressed is kept and suppresses every later one with (xi-xj)*(xi-xj) + (yi-yj)*(yi-yj) <= radius in fp32 (the
+ *     squared distance against the radius itself, as the reference's circle_nms compares).  radius: HOST float
+ *     [n_radius]; segment s uses radius[s % n_radius].  keep int32 [n_segments, post_max]: the indices inside the
+ *     segment of the first post_max kept entries, in kept order (the rest of a row is not written); count int32
+ *     [n_segments].
+ *   boxes: for segment s and k < count[s], row s * post_max + k of boxes [batch * n_tasks * post_max, 9 or 7 without vel]
+ *     = (x, y, height, exp(dim0..2), vel0..1, atan2(rot0, rot1)) of cell keep[s, k], scores = its score, labels = its
+ *     label + the number of classes of the tasks before; other rows are not written. */
+int efg_center_decode_max_cells(void);
+int efg_center_decode_max_tasks(void);
+int efg_center_decode_candidates_f32(const void* const* maps, const int32_t* num_classes, int n_tasks, int batch, int h,
+                                     int w, float out_size_factor, float voxel_x, float voxel_y, float range_x,
+                                     float range_y, float score_threshold, const float* limit, float* score,
+                                     int32_t* label, float* x, float* y, void* stream);
+int efg_circle_nms_f32(const float* x, const float* y, const float* score, int n_segments, int segment_len,
+                       const float* radius, int n_radius, int post_max, int32_t* keep, int32_t* count, void* stream);
+int efg_center_decode_boxes_f32(const void* const* maps, const int32_t* num_classes, int n_tasks, int batch, int h, int w,
+                                int post_max, const float* x, const float* y, const float* score, const int32_t* label,
+                                const int32_t* keep, const int32_t* count, float* boxes, float* scores, int32_t* labels,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif
