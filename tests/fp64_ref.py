@@ -170,7 +170,7 @@ def _corners(px, py):
     return out
 
 
-def sample_fp64(value, shapes, starts, loc, attn, grad_out=None, geo_ulps=GEO_ULPS):
+def sample_fp64(value, shapes, starts, loc, attn, grad_out=None, geo_ulps=GEO_ULPS, reference_inside=False):
     """Multi-scale bilinear sampling (the sampling op of box / deformable attention) in float64, written out by hand.
 
     value [B, S, H, D], shapes [L, 2] (h, w), starts [L], loc [B, Q, H, L, P, 2] normalised (x, y), attn [B, Q, H, L, P],
@@ -184,7 +184,12 @@ def sample_fp64(value, shapes, starts, loc, attn, grad_out=None, geo_ulps=GEO_UL
     the map -- in whichever direction hurts, computed in fp64.  It is first order only: with no sampling point within
     1e-3 px of a cell boundary both sides interpolate between the same four corners.  The bilinear weight is linear in each
     coordinate, so the geometry term of grad_loc is the mixed second derivative (|d2 w / dpx dpy| = 1).  grad_value_n:
-    the number of (point, corner) entries summed into each grad_value row."""
+    the number of (point, corner) entries summed into each grad_value row.
+
+    `reference_inside` (default off) applies the rule of the kernels and of the CUDA reference (box_attn_kernel.cuh) to the
+    WHOLE point: a point takes part only if px > -1 && py > -1 && px < W && py < H.  It differs from the per-corner rule
+    only at px == -1 or py == -1 exactly, where the one corner in range has weight 0 but a one-sided derivative of the
+    weight that is not 0: with the keyword such a point contributes nothing, grad_loc included."""
     b, s, h, d = value.shape
     q, nl, p = loc.shape[1], loc.shape[3], loc.shape[4]
     dev = value.device
@@ -211,8 +216,12 @@ def sample_fp64(value, shapes, starts, loc, attn, grad_out=None, geo_ulps=GEO_UL
         dpx = geo_ulps * 2.0 ** -23 * torch.clamp(px.abs(), min=float(wl))
         dpy = geo_ulps * 2.0 ** -23 * torch.clamp(py.abs(), min=float(hl))
         al = a[:, :, :, lv, :]
+        if reference_inside:
+            whole = ((px > -1) & (py > -1) & (px < wl) & (py < hl)).to(torch.float64)
         for cx, cy, wgt, dwx, dwy in _corners(px, py):
             inside = ((cx >= 0) & (cx < wl) & (cy >= 0) & (cy < hl)).to(torch.float64)
+            if reference_inside:
+                inside = inside * whole
             row = base + st + (cy.clamp(0, hl - 1) * wl + cx.clamp(0, wl - 1)).long()   # [B, Q, H, P]
             vc = vflat[row] * inside.unsqueeze(-1)                                      # [B, Q, H, P, D]
             vca = vc.abs()
