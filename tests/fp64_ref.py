@@ -1,5 +1,6 @@
 """Plain float64 references for the sparse convolution, the fused box attention, the detection-loss tail (matching
-cost, focal loss, box loss) and the normalisation kernels (BatchNorm (+ residual) (+ ReLU) with its running statistics,
+cost, focal loss, box loss), scaled-dot-product attention with a boolean mask (forward, log-sum-exp and backward, written out from
+the softmax) and the normalisation kernels (BatchNorm (+ residual) (+ ReLU) with its running statistics,
 channels-last GroupNorm, residual-add + LayerNorm; written out from mean, biased variance and rstd, forward and backward),
 and an element-wise error bar.
 
@@ -716,3 +717,86 @@ def add_layernorm_fp64(x, residual, w, b, eps, dy):
         for t in ("", "_mag", "_cond", "_n"):
             res["dresidual" + t] = res["dx" + t]
     return res
+
+
+# ---- attention: softmax(scale Q K^T, masked) V and its gradients (csrc/attention.hip) -----------------------------------------
+# Written out from the definition: s = scale q k^T, a masked pair takes no part, lse = log sum_j exp(s_ij), p = exp(s - lse),
+# out = p v; backward: dv = p^T dO, dP = dO v^T, D_i = sum_x dO_ix out_ix, dS = p (dP - D), dq = scale dS k, dk = scale dS^T q.
+# A query with no allowed key has p = 0 throughout: out, dq and its share of dk and dv are exactly 0, lse = -inf.  Nothing of
+# efg_amd and no torch softmax / logsumexp / autograd is used.
+# `_mag` is the same sum over absolute values, `_n` the number of terms of the element's last sum (allowed keys of the query for
+# out and dq, allowed queries of the key for dk and dv) and `_cond` an ABSOLUTE allowance for assert_elementwise's `geo64`.  A
+# softmax is ill-conditioned in its logits: ANY fp32 evaluation from the fixed fp32 inputs rounds the logit, the row's
+# log-sum-exp (or max and sum) and the exponential, and a change e of the exponent moves p by p e.  With u = 2^-24 and d the head
+# width, independent roundings added in quadrature, the exponent of an allowed pair is uncertain by
+#   delta_ij = u (sqrt(d) scale sqrt(sum_x q_ix^2 k_jx^2)    the d products of the dot product, each rounded once
+#               + |s_ij|                                      the rounded factor scale (* log2 e) folded into one operand
+#               + |lse_i|                                     the log-sum-exp stored (or the running max held) in fp32
+#               + |s_ij - lse_i|                              the subtraction's result
+#               + 2)                                          a 1-ulp exp (2^-23 relative) -- delta_ij = 0 for a masked pair
+# The row's normaliser is the sum of the p_ij: a_i = sqrt(sum_j (p_ij delta_ij)^2) in relative terms.  So p_ij carries
+# F_ij = p_ij (delta_ij + a_i), and out_cond = sqrt(F^2 v^2), dv_cond = sqrt(F^2^T dO^2), lse_cond = a_i + 2 u |lse_i| (the log
+# and the stored value).  dS = p (dP - D) carries
+#   E_ij = |dS_ij| (delta_ij + a_i)                                       the error of p_ij
+#        + p_ij sqrt(sum_j' (dS_ij' delta_ij')^2)                         D_i = sum_j p_ij dP_ij moves with every p_ij' of the row
+#        + p_ij (sqrt(d) u sqrt(sum_x dO_ix^2 v_jx^2) + Derr_i)           the d products of dP_ij; the rounded D_i
+#        + 2 u |dS_ij|                                                    the subtraction and the product
+# with Derr_i = sqrt(sum_x (|dO_ix| (out_cond + sqrt(n) u out_mag)_ix)^2) + sqrt(d) u sqrt(sum_x (dO_ix out_ix)^2): D_i is taken
+# from the ROUNDED fp32 out and is a sum of d products.  dq_cond = scale sqrt(E^2 k^2), dk_cond = scale sqrt(E^2^T q^2).  `_cond`
+# never sees a kernel's output.  Unlike the worst-case sums of the detection-loss and norm sections it is a QUADRATURE -- the size
+# of one standard deviation when every rounding is as large as it can be -- so a test passes geo64 = c * cond: the bar is
+# c (sqrt(n) 2^-24 |terms| + cond), one constant over both root-sum-square estimates (attention_fp64_cases.check_against).
+def attention_fp64(q, k, v, grad_out, scale, mask=None):
+    """Scaled-dot-product attention and its gradients in float64.  q, grad_out [B, H, Sq, D], k, v [B, H, Sk, D] (any strides),
+    mask bool [Sq, Sk] (True = not attended) or None.  Returns a dict: out [B, H, Sq, D], lse [B, H, Sq], dq, dk, dv like q, k, v,
+    each with `_mag`, `_n` and `_cond` (see the section comment); live [Sq] bool: queries with at least one allowed key."""
+    q64, k64, v64, g64 = (t.detach().to(torch.float64) for t in (q, k, v, grad_out))
+    dev = q64.device
+    sq, sk, d = q64.shape[2], k64.shape[2], q64.shape[3]
+    scale = float(scale)
+    allowed = torch.ones(sq, sk, dtype=torch.bool, device=dev) if mask is None else ~mask.to(dev)
+    al = allowed.to(torch.float64)
+    live = allowed.any(1)
+    lv = live.view(1, 1, sq, 1)
+    kt, vt = k64.transpose(-1, -2), v64.transpose(-1, -2)
+    s = scale * (q64 @ kt)                                                          # [B, H, Sq, Sk]
+    s_m = s.masked_fill(~allowed, -math.inf)
+    m0 = torch.where(lv, s_m.max(-1, keepdim=True).values, torch.zeros((), dtype=torch.float64, device=dev))
+    e = torch.exp(s_m - m0)                                                         # a masked pair: exp(-inf) = 0
+    l = e.sum(-1, keepdim=True)
+    p = e / l.clamp_min(1e-300)                                                     # a dead row: 0 / tiny = 0
+    lse0 = (m0 + torch.log(l.clamp_min(1e-300))) * lv                               # 0 in dead rows
+    lse = torch.where(lv, lse0, torch.full((), -math.inf, dtype=torch.float64, device=dev)).squeeze(-1)
+    out = p @ v64
+    n_q = al.sum(1).view(1, 1, sq, 1)
+    n_k = al.sum(0).view(1, 1, sk, 1)
+
+    delta = U32 * (math.sqrt(d) * scale * torch.sqrt((q64 ** 2) @ (kt ** 2)) + s.abs() + lse0.abs() + (s - lse0).abs() + 2.0) * al
+    a = torch.sqrt(((p * delta) ** 2).sum(-1, keepdim=True))
+    f2 = (p * (delta + a)) ** 2
+    out_mag = p @ v64.abs()
+    out_cond = torch.sqrt(f2 @ v64 ** 2)
+    dv = p.transpose(-1, -2) @ g64
+    dv_mag = p.transpose(-1, -2) @ g64.abs()
+    dv_cond = torch.sqrt(f2.transpose(-1, -2) @ g64 ** 2)
+    lse_cond = (a + 2 * U32 * lse0.abs()).squeeze(-1)
+
+    dp = g64 @ vt
+    dd = (g64 * out).sum(-1, keepdim=True)
+    ds = p * (dp - dd)
+    d_err = torch.sqrt(((g64.abs() * (out_cond + torch.sqrt(n_q.clamp_min(1.0)) * U32 * out_mag)) ** 2).sum(-1, keepdim=True)) \
+        + math.sqrt(d) * U32 * torch.sqrt(((g64 * out) ** 2).sum(-1, keepdim=True))
+    err = ds.abs() * (delta + a) + p * torch.sqrt(((ds * delta) ** 2).sum(-1, keepdim=True)) \
+        + p * (math.sqrt(d) * U32 * torch.sqrt((g64 ** 2) @ (vt ** 2)) + d_err) + 2 * U32 * ds.abs()
+    e2 = err ** 2
+    dq = scale * (ds @ k64)
+    dq_mag = scale * (ds.abs() @ k64.abs())
+    dq_cond = scale * torch.sqrt(e2 @ k64 ** 2)
+    dk = scale * (ds.transpose(-1, -2) @ q64)
+    dk_mag = scale * (ds.abs().transpose(-1, -2) @ q64.abs())
+    dk_cond = scale * torch.sqrt(e2.transpose(-1, -2) @ q64 ** 2)
+    return dict(out=out, out_mag=out_mag, out_n=n_q, out_cond=out_cond,
+                lse=lse, lse_mag=torch.zeros_like(lse), lse_n=1, lse_cond=lse_cond,
+                dq=dq, dq_mag=dq_mag, dq_n=n_q, dq_cond=dq_cond,
+                dk=dk, dk_mag=dk_mag, dk_n=n_k, dk_cond=dk_cond,
+                dv=dv, dv_mag=dv_mag, dv_n=n_k, dv_cond=dv_cond, live=live)
