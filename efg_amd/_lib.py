@@ -148,6 +148,13 @@ _SIGS = {
     "efg_center_decode_candidates_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_float] * 6 + [c_void_p] * 6),
     "efg_circle_nms_f32": (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p, c_int, c_int] + [c_void_p] * 3),
     "efg_center_decode_boxes_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p] * 10),
+    "efg_pillar_workspace_bytes": (c_size_t, []),
+    "efg_pillar_forward_f32": (c_int, [c_void_p] * 9 + [c_float, c_float, c_int64] + [c_int] * 4 + [c_float] * 4 + [c_int] +
+                               [c_void_p] * 5 + [c_size_t, c_int, c_void_p]),
+    "efg_pillar_backward_f32": (c_int, [c_void_p] * 10 + [c_int64] + [c_int] * 4 + [c_float] * 4 + [c_int] + [c_void_p] * 4 +
+                                [c_size_t, c_int, c_void_p]),
+    "efg_pillar_scatter_f32": (c_int, [c_void_p, c_void_p, c_int64] + [c_int] * 4 + [c_void_p, c_void_p]),
+    "efg_pillar_gather_f32": (c_int, [c_void_p, c_void_p, c_int64] + [c_int] * 4 + [c_void_p, c_void_p]),
 }
 
 # the split-precision GEMM arms (csrc/gemm_split_bf16.h): one set of six signatures under two prefixes

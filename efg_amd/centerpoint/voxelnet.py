@@ -27,8 +27,7 @@ class VoxelNet(nn.Module):
         super().__init__()
         self.config = config
         self.device = torch.device(config.model.device)
-        self.reader = VoxelMeanFeatureExtractor(**config.model.reader)
-        self.backbone = SpMiddleResNetFHD(**config.model.backbone)
+        self._build_reader_and_backbone(config)
         self.neck = RPN(config.model.neck)
         self.center_head = CenterHead(config)
         lc = config.model.loss
@@ -46,6 +45,16 @@ class VoxelNet(nn.Module):
         if self.device.type == "cuda":
             self.neck.to(memory_format=torch.channels_last)
             self.center_head.to(memory_format=torch.channels_last)
+
+    # ---- the two stages a subclass swaps (centerpoint/pointpillars.py) ---------------------------------------------
+    def _build_reader_and_backbone(self, config):
+        self.reader = VoxelMeanFeatureExtractor(**config.model.reader)
+        self.backbone = SpMiddleResNetFHD(**config.model.backbone)
+
+    def _bev(self, feats, coors, batch_size, grid):
+        """What `_inputs` returned -> the BEV map the neck takes."""
+        with spconv_core.geometry_stream(self._geometry_stream()):
+            return self.backbone(feats, coors, batch_size, grid)
 
     # ---- inputs -------------------------------------------------------------------------------------------------
     def _geometry_stream(self):
@@ -107,8 +116,7 @@ class VoxelNet(nn.Module):
         with torch.no_grad():
             feats, coors, batch_size, grid, pc_range, voxel_size = self._inputs(samples)
             targets = self.label_assign(infos, grid, pc_range, voxel_size) if self.training else None
-        with spconv_core.geometry_stream(self._geometry_stream()):
-            x = self.backbone(feats, coors, batch_size, grid)
+        x = self._bev(feats, coors, batch_size, grid)
         x = self.neck(x)
         preds = self.center_head(x)
         if self.training:

@@ -6,7 +6,8 @@
 `from efg.data.augmentations3d import _dict_select` (the stale path at $CP1/voxelnet.py:9),
 `import spconv.pytorch as spconv`,
 `from efg.modeling.backbones.fpn import build_resnet_fpn_backbone` and
-`from efg.modeling.readers.voxel_reader import VoxelMeanFeatureExtractor` resolve to the MI355X
+`from efg.modeling.readers.voxel_reader import VoxelMeanFeatureExtractor` and
+`from efg.modeling.readers.pillar_encoder import PillarFeatureNet, PointPillarsScatter` resolve to the MI355X
 implementations.  Nothing is installed unless the caller asks for it, and an existing real `efg` /
 `spconv` package is never overwritten."""
 import sys
@@ -30,7 +31,7 @@ def install(force=False):
     from . import _C, data, modeling, operators, spconv
     from .modeling import backbones, common, readers
     from .modeling.backbones import fpn, sparse_net
-    from .modeling.readers import voxel_reader
+    from .modeling.readers import pillar_encoder, voxel_reader
     from .operators import box_attention_func, iou3d_nms, ms_deform_attn, scatter_points, voxelize
 
     aug3d = types.ModuleType("efg.data.augmentations3d")
@@ -69,6 +70,7 @@ def install(force=False):
         "efg.modeling.backbones.sparse_net": sparse_net,
         "efg.modeling.readers": readers,
         "efg.modeling.readers.voxel_reader": voxel_reader,
+        "efg.modeling.readers.pillar_encoder": pillar_encoder,
         "spconv": spconv,
         "spconv.pytorch": spconv,
     }

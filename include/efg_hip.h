@@ -751,6 +751,42 @@ int efg_center_decode_boxes_f32(const void* const* maps, const int32_t* num_clas
                                 const int32_t* keep, const int32_t* count, float* boxes, float* scores, int32_t* labels,
                                 void* stream);
 
+/* ---- PointPillars reader (pillars.hip, DESIGN.md "PointPillars reader") ----
+ * The one-layer PillarFeatureNet fused: decorate -> Linear(Cin, 64, no bias) -> BatchNorm1d -> ReLU -> max over the rows.
+ * voxels [p, n, f] fp32 (16-byte aligned), num_points int32 [p] (>= 1: a precondition, the voxelizer guarantees it),
+ * coors int32 [p, 4] (b, z, y, x), weight [cout, cin] with cin = f + 5 (+ 1 with_distance), gamma / beta [cout].
+ * Limits, checked before anything is launched: cout == 64, 1 <= n <= 64, 3 <= f <= 11, cin <= 16.  p == 0 launches nothing.
+ * Decorated row n < num_points: [raw, xyz - mean, x - ((float)coors[3] * vx + x_offset), y - ((float)coors[2] * vy +
+ * y_offset) (, |xyz|)], mean = (sum of xyz over ALL n rows) / num_points; a row n >= num_points is zero after decoration
+ * whatever it holds and enters BatchNorm with the pre-activation 0.
+ *   forward, batch_stats != 0: mean / rstd [cout] are WRITTEN from the batch (p * n entries per channel, fp64 moments added
+ *     in a fixed order) and, unless NULL, running_mean / running_var (unbiased, momentum) and num_batches_tracked (+ 1) are
+ *     updated.  batch_stats == 0: mean / rstd are READ (the caller's running statistics), nothing else is touched.
+ *     out [p, cout] = max over the n rows of relu(bn(x)), index uint8 [p, cout] = the lowest row that attains it.
+ *   backward: from dy [p, cout] and the forward's index, mean, rstd: dweight [cout, cin], dgamma, dbeta [cout] (through the
+ *     batch statistics iff batch_stats != 0).  No gradient to the points.  p must be > 0.
+ * ws: efg_pillar_workspace_bytes().  max_blocks > 0 lowers the cap of the looped grids (tests); 0 = the default.
+ * No atomics: every output is bit-reproducible.
+ *   scatter: canvas [batch, ny, nx, c] (the memory of a channels-last [batch, c, ny, nx]; zero-filled by the caller) gets
+ *     feats[p] at cell (coors[p, 0], coors[p, 2], coors[p, 3]); gather is its backward, feats[p] = canvas[cell].  A
+ *     coordinate outside the canvas is skipped (gather: a zero row). */
+size_t efg_pillar_workspace_bytes(void);
+int efg_pillar_forward_f32(const float* voxels, const int32_t* num_points, const int32_t* coors, const float* weight,
+                           const float* gamma, const float* beta, float* running_mean, float* running_var,
+                           int64_t* num_batches_tracked, float momentum, float eps, int64_t p, int n, int f,
+                           int with_distance, int cout, float vx, float vy, float x_offset, float y_offset,
+                           int batch_stats, float* mean, float* rstd, float* out, uint8_t* index, void* ws,
+                           size_t ws_bytes, int max_blocks, void* stream);
+int efg_pillar_backward_f32(const float* voxels, const int32_t* num_points, const int32_t* coors, const float* weight,
+                            const float* gamma, const float* beta, const float* mean, const float* rstd, const float* dy,
+                            const uint8_t* index, int64_t p, int n, int f, int with_distance, int cout, float vx, float vy,
+                            float x_offset, float y_offset, int batch_stats, float* dweight, float* dgamma, float* dbeta,
+                            void* ws, size_t ws_bytes, int max_blocks, void* stream);
+int efg_pillar_scatter_f32(const float* feats, const int32_t* coors, int64_t p, int c, int batch, int ny, int nx,
+                           float* canvas, void* stream);
+int efg_pillar_gather_f32(const float* canvas, const int32_t* coors, int64_t p, int c, int batch, int ny, int nx,
+                          float* feats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
