@@ -10,6 +10,11 @@
 // Same lane mapping as msda.hip (LP = D/4 lanes x float4 per pair).  Encoder self-attention (queries on the
 // value grid, L*P <= 32) has its own backward in GEMM form, box_bwd_tile_a_kernel + box_bwd_tile_b_kernel below; larger point counts
 // accumulate grad_value in an fp64 LDS window like msda_bwd_grid_kernel.
+//
+// Every arm is checked per element against fp64 by tests/test_box_fused_fp64_gpu.py.  It found one bug, in the host code of
+// the backward: an empty call (B = 0 or Lq = 0) returned before anything had written the workspace's overflow word, which the
+// Python op reads after every call when it checks the bins, so an empty batch could be reported as overflowed bins from
+// stale memory.  The early return now zeroes the word.
 #include "common.h"
 #include <algorithm>
 #include <cmath>
@@ -1261,7 +1266,12 @@ extern "C" int efg_box_attn_fused_backward_strided_f32(const float* value, const
   if (int rc = set_strides(&dm, off_row_stride, logit_row_stride)) return rc;   // (the gradients have the strides of their matrices)
   EFG_CHECK_ARG(d == 32, "box_attn_fused backward: head dim 32 only (got %d); use the unfused op", d);
   const long long total = (long long)b * lq * h;
-  if (total == 0) return EFG_OK;
+  if (total == 0) {
+    // nothing to launch, but the overflow word is defined whenever a workspace is given: the Python op reads it after every
+    // call when it checks the bins, and an empty call (B = 0 or Lq = 0) used to leave it uninitialised
+    if (ws != nullptr && ws_bytes >= sizeof(int)) EFG_HIP_TRY(hipMemsetAsync(ws, 0, sizeof(int), (hipStream_t)stream));
+    return EFG_OK;
+  }
   if (l == 1 && s == lq && s >= 1024 && h <= 65535 && b <= 65535) {
     // encoder self-attention (queries on the value map): fp64 LDS window per 8x8 query tile.  H, W are
     // device-side, so the launch is sized for a square map and the kernel strides over the tiles.

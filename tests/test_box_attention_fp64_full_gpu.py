@@ -13,7 +13,8 @@ interpolate between the same four corners; a few per cent of the (query, head) r
 import pytest
 import torch
 
-from fp64_ref import assert_elementwise, binned_sum_allowance, box_attention_fp64, log_uniform_signed, near_cell_boundary
+from box_fp64_cases import out_of_window_share, pixels, redraw_kinks
+from fp64_ref import assert_elementwise, binned_sum_allowance, box_attention_fp64, log_uniform_signed
 
 pytestmark = pytest.mark.gpu
 
@@ -29,47 +30,6 @@ def _lattice():
     from efg_amd.detection3d.box_attention import _lattice
 
     return _lattice(5)
-
-
-def _pixels(ref, offsets, kidx, rot, hm, wm):
-    from efg_amd.operators.box_attention_func import box_sampling_grid
-
-    grid = box_sampling_grid(ref.double(), offsets.double(), kidx.double(), H, L, rot)
-    return grid[..., 0] * wm - 0.5, grid[..., 1] * hm - 0.5          # [B, Q, H, L, P]
-
-
-def _redraw_kinks(ref, offsets, kidx, rot, hm, wm, gen):
-    """New offsets for every (query, head) with a sampling point within 1e-3 px of a cell boundary; returns the share of
-    sampling points that were that close in the first draw."""
-    nvar = 5 if rot else 4
-    first = None
-    for _ in range(20):
-        near = near_cell_boundary(*_pixels(ref, offsets, kidx, rot, hm, wm))
-        if first is None:
-            first = float(near.float().mean())
-        rows = near.any(-1)
-        if not bool(rows.any()):
-            return first
-        off = offsets.view(B, -1, H, L, nvar)
-        off[rows] = (torch.randn(int(rows.sum()), nvar, generator=gen) * 0.5).to(off.device)
-    raise AssertionError("sampling points keep landing on cell boundaries")
-
-
-def _out_of_window_share(px, py, hm, wm):
-    """Share of the in-map corners outside the 12 x 16 window of their query's 4 x 8 tile (tile + 4 cells each side)."""
-    q = torch.arange(hm * wm, device=px.device)
-    wx0 = ((q % wm) // 8 * 8 - 4).view(1, -1, 1, 1, 1)
-    wy0 = ((q // wm) // 4 * 4 - 4).view(1, -1, 1, 1, 1)
-    x0, y0 = torch.floor(px), torch.floor(py)
-    n_in = n_out = 0
-    for dy in (0, 1):
-        for dx in (0, 1):
-            cx, cy = x0 + dx, y0 + dy
-            inside = (cx >= 0) & (cx < wm) & (cy >= 0) & (cy < hm)
-            away = (cx < wx0) | (cx > wx0 + 15) | (cy < wy0) | (cy > wy0 + 11)
-            n_in += int(inside.sum())
-            n_out += int((inside & away).sum())
-    return n_out / n_in
 
 
 def _run(dev, tag, hm, wm, ref, value, offsets, logits, kidx, nvar, gout, shared):
@@ -138,10 +98,10 @@ def test_encoder_tile_path_against_fp64(dev, map_name, regime):
     gen = torch.Generator().manual_seed(100 + list(ENCODER).index((map_name, regime)))
     ref, value, offsets, logits, gout, nvar = _encoder_case(dev, hm, wm, regime, rot, gen)
     kidx = _lattice().to(dev)
-    near = _redraw_kinks(ref, offsets, kidx, rot, hm, wm, gen)
+    near = redraw_kinks(ref, offsets, kidx, rot, [[hm, wm]], H, gen)
     assert near < 0.01, near
-    px, py = _pixels(ref, offsets, kidx, rot, hm, wm)
-    share = _out_of_window_share(px, py, hm, wm)
+    px, py = pixels(ref, offsets, kidx, rot, [[hm, wm]], H)
+    share = out_of_window_share(px, py, hm, wm)
     print("%s %s: %.3f of the in-map corners outside their tile window, %.4f of the points redrawn" % (
         map_name, regime, share, near))
     # measured (fp64 geometry of these draws): anchor 0.000 / 0.000, grown 0.640 / 0.285 (rotated), heavy 0.189 / 0.105
@@ -171,6 +131,6 @@ def test_decoder_binned_path_against_fp64(dev, grad):
             log_uniform_signed((B, lq, H * D), 1e-6, 1e2, gen))
     ref, value, offsets, logits, gout = (t.to(dev) for t in (ref, value, offsets, logits, gout))
     kidx = _lattice().to(dev)
-    near = _redraw_kinks(ref, offsets, kidx, True, hm, wm, gen)
+    near = redraw_kinks(ref, offsets, kidx, True, [[hm, wm]], H, gen)
     assert near < 0.01, near
     _run(dev, "decoder %s" % grad, hm, wm, ref, value, offsets, logits, kidx, nvar, gout, shared=(grad == "normal"))
